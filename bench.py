@@ -14,8 +14,16 @@ on the kernel stream ahead of the warp): the host consensus of step k runs while
 k-1's frames are warped; every step still runs every stage, and the pipeline is drained
 inside the timed region.  --serial runs the steps strictly one after another.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, RCCL)
+
+A plain run sets up, warms up, times the K steps and prints the result line (the figures in
+it beside `value` come from HIP events the timed steps record anyway).  --full adds what
+takes runs of its own after the timed region: every GPU stage alone (`stage_ms_isolated`,
+the RANSAC / match / isolated-warp rooflines, `ransac_hypotheses_per_s_per_gpu`) and the
+CPU baseline (`cpu_baseline`, see --cpu-sample / --cpu-procs).  --dump-outputs DIR writes
+what the last timed step returned to its caller as DIR/<name>.npy (dump_outputs below); the
+inputs are seeded, so two builds run with the same arguments compare output for output.
 
 Without torchrun, `--gpus N > 1` starts the N rank processes itself (spawn_ranks: before
 any GPU call, one child per GPU with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*), and refuses
@@ -151,10 +159,9 @@ class StageTimer:
 
 def run_step(inp, cfg, out, timer=None, world=1, counts=None):
     """One pass of the hot path, strictly in order (--serial; single GPU or this rank's
-    share of a sharded run through distributed.align_sharded)."""
+    share of a sharded run through distributed.align_sharded).  Returns the SlabResult."""
     if world > 1:
-        res = kdist.align_sharded(inp, cfg, counts=counts)
-        return res.consensus, None
+        return kdist.align_sharded(inp, cfg, counts=counts)
     mark = timer.mark if timer else (lambda name, ev=None: None)
     n_tpl = inp.des_tpl.shape[0]
     mark("m0")
@@ -167,9 +174,60 @@ def run_step(inp, cfg, out, timer=None, world=1, counts=None):
     affines, skipped, interp, eu = pipeline.postprocess_affines(rr.params.cpu().numpy(), cfg)
     a_dev = torch.from_numpy(np.ascontiguousarray(affines[: inp.frames.shape[0]])).to(inp.frames.device)
     mark("w0")
-    pipeline.warp_frames(inp.frames, a_dev, out=out)
+    aligned = pipeline.warp_frames(inp.frames, a_dev, out=out)
     mark("w1")
-    return cons, rr
+    return pipeline.SlabResult(aligned, affines, eu, skipped, interp, match=m, consensus=cons, ransac=rr)
+
+
+DUMP_SAMPLE_ELEMENTS = 4 << 20  # aligned-frame sample: 16 MB as float32
+DUMP_SAMPLE_SEED = 20240607
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def sample_elements(t: torch.Tensor, n: int = DUMP_SAMPLE_ELEMENTS, seed: int = DUMP_SAMPLE_SEED) -> np.ndarray:
+    """float32 copy of `t` (a uint16 frame stack on the device) when it has at most n elements,
+    else of n of its elements: flat positions drawn once from `seed` (the same for every run
+    of the same shape), sorted, so every frame is sampled at a few thousand pixels."""
+    flat = t.reshape(-1).view(torch.int16)  # the bits; uint16 has no gather kernel
+    if flat.numel() > n:
+        pos = np.sort(np.random.default_rng(seed).integers(0, flat.numel(), n, dtype=np.int64))
+        flat = flat[torch.from_numpy(pos).to(flat.device)]
+    return flat.cpu().numpy().view(np.uint16).astype(np.float32)
+
+
+def dump_outputs(dirpath: str, aligned, res, n_frames: int, suffix: str = "") -> None:
+    """Write what the last timed step handed to its caller as <dirpath>/<name><suffix>.npy:
+    `aligned_sample` (float32; sample_elements of every aligned stack in `aligned`, one after
+    another) and, in float64, `affines` [F, 2, 3] / `euclidean` [F, 3] (after gap
+    interpolation), `skipped` and `interpolated` ([F] 0/1 masks), and where the path returns
+    them the consensus (`consensus_order`, `consensus_votes`, CSR point lists `pt_off` /
+    `pt_idx`) and the RANSAC results (`ransac_params`, NaN where no model; `ransac_n_inliers`)."""
+    os.makedirs(dirpath, exist_ok=True)
+    stacks = aligned if isinstance(aligned, (list, tuple)) else [aligned]
+    share = DUMP_SAMPLE_ELEMENTS // len(stacks)
+    arrays = {"aligned_sample": np.concatenate([sample_elements(a, share) for a in stacks]),
+              "affines": np.asarray(res.affines, dtype=np.float64),
+              "euclidean": np.asarray(res.euclidean, dtype=np.float64)}
+    f0 = getattr(res, "extras", {}).get("f0", 0)  # a rank's slab lists global frame indices
+    for name in ("skipped", "interpolated"):
+        mask = np.zeros(n_frames, np.float64)
+        idx = np.asarray(getattr(res, name), dtype=np.int64) - f0
+        mask[idx[(idx >= 0) & (idx < n_frames)]] = 1.0
+        arrays[name] = mask
+    cons = getattr(res, "consensus", None)
+    if cons is not None:
+        arrays.update(consensus_order=cons.order, consensus_votes=cons.votes, pt_off=cons.pt_off, pt_idx=cons.pt_idx)
+    rr = getattr(res, "ransac", None)
+    if rr is not None:
+        arrays.update(ransac_params=rr.params.cpu().numpy(), ransac_n_inliers=rr.n_inliers.cpu().numpy())
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32 if name == "aligned_sample" else np.float64)
+        total += a.nbytes
+        if total > DUMP_LIMIT_BYTES:
+            raise SystemExit(f"bench.py: --dump-outputs would write more than {DUMP_LIMIT_BYTES >> 20} MB")
+        np.save(os.path.join(dirpath, f"{name}{suffix}.npy"), a)
+    log(f"dumped {len(arrays)} arrays ({total / 1e6:.1f} MB) to {dirpath}")
 
 
 def isolated_stage_ms(inp, cfg, out, reps=7):
@@ -509,11 +567,8 @@ def single_process(args, bc: BenchConfig) -> dict:
     elapsed = time.perf_counter() - t0
     total = args.frames * len(devices)
     ms_step = 1e3 * elapsed / args.steps
-    out0 = torch.empty_like(slabs[0].frames)
-    torch.cuda.set_device(slabs[0].frames.device)
-    iso, _ = isolated_stage_ms(slabs[0], cfg, out0)
-    warp_bytes = 2 * slabs[0].frames.numel() * slabs[0].frames.element_size()
-    achieved = warp_bytes / (iso["warp"] * 1e-3) / 1e9
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res.aligned, res, total)
     result = {
         "metric": METRIC, "value": round(total * args.steps / elapsed, 1), "unit": "frames/s",
         "n_gpus": len(set(devices)), "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_step, 3),
@@ -523,15 +578,83 @@ def single_process(args, bc: BenchConfig) -> dict:
         "config": {"workload": bc.workload, "frames_per_slab": args.frames, "devices": devices,
                    "parallelism": f"single-process split x{len(devices)} (VideoAligner drop-in path)"},
         "skipped_frames": len(res.skipped),
-        "stage_ms_isolated_slab0": iso,
-        "roofline": {"kernel": (f"warp_perspective_u16_kernel<{bc.C}>" if bc.model == "projective"
-                                else f"warp_affine_u16_kernel<{bc.C}>"), "bound": "hbm",
-                     "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
-                     "algorithmic_bytes_per_launch": warp_bytes, "avg_launch_ms": iso["warp"],
-                     "note": "slab 0's warp alone (median of per-dispatch HIP events)"},
     }
+    if args.full:  # slab 0's stages alone: runs of their own after the timed region
+        out0 =torch.empty_like(slabs[0].frames)
+        torch.cuda.set_device(slabs[0].frames.device)
+        iso, _ = isolated_stage_ms(slabs[0], cfg, out0)
+        warp_bytes = 2 * slabs[0].frames.numel() * slabs[0].frames.element_size()
+        achieved = warp_bytes / (iso["warp"] * 1e-3) / 1e9
+        result["stage_ms_isolated_slab0"] = iso
+        result["roofline"] = {"kernel": (f"warp_perspective_u16_kernel<{bc.C}>" if bc.model == "projective"
+                                         else f"warp_affine_u16_kernel<{bc.C}>"), "bound": "hbm",
+                              "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                              "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
+                              "algorithmic_bytes_per_launch": warp_bytes, "avg_launch_ms": iso["warp"],
+                              "note": "slab 0's warp alone (median of per-dispatch HIP events)"}
     return result
+
+
+def full_figures(result: dict, bc: BenchConfig, inp, cfg, out, warp_bytes: int) -> None:
+    """--full: every GPU stage alone after the timed region (isolated_stage_ms) and the
+    figures priced on those times, added to the result line."""
+    iso, iso_cons = isolated_stage_ms(inp, cfg, out)
+    iso_pts = np.diff(iso_cons.pt_off)
+    iso_ransac = int((iso_pts >= cfg.effective_frame_skip).sum())
+    # RANSAC kernel alone; the overlapped figure shares the CUs with the previous step's warp
+    result["ransac_hypotheses_per_s_per_gpu"] = round(iso_ransac * TRIALS / (iso["ransac"] * 1e-3), 1)
+    result["roofline_ransac"] = ransac_roofline(bc.model, iso_cons, cfg, iso["ransac"])
+    result["stage_ms_isolated"] = iso
+    # the warp's own roofline: the same launch alone, median of per-dispatch HIP event
+    # pairs (the timed steps run RANSAC beside it, which `roofline` includes)
+    result["roofline_isolated"] = {"kernel": "warp_plan_kernel + " + ("warp_perspective_u16_kernel"
+                                                                     if cfg.ransac_model == "projective" else
+                                                                     "warp_affine_u16_kernel"),
+                                   "achieved": round(warp_bytes / (iso["warp"] * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS,
+                                   "unit": "GB/s",
+                                   "frac": round(warp_bytes / (iso["warp"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                   "median_launch_ms": iso["warp"]}
+    # the matcher against its rooflines (the dominant kernel of c5): algorithmic work
+    # 2 * n_tpl * n_q * D per frame.  The float matcher issues one fp16 product per fp32
+    # product (a certified candidate search; exact fp64 re-rank of 2-3 candidates), priced
+    # against fp16 dense (= bf16 dense); its bound is the top-8 selection on VALU, reported
+    # beside it against 8 integer VALU per distance (round 3's reference count, kept so the
+    # fraction compares across rounds)
+    n_q_total = float(inp.q_off_host[-1])
+    match_ops = 2.0 * bc.n_tpl * n_q_total * bc.D
+    iso_match_s = iso["match"] * 1e-3
+    if bc.descriptor == "f32":
+        issued = match_ops / iso_match_s / 1e12
+        dists = match_ops / (2.0 * bc.D) / iso_match_s / 1e12
+        valu_peak = VALU_INSTR_PER_S_PER_GPU * 64 / 8.0 / 1e12
+        result["roofline_match"] = {
+            "kernel": "tpl_stats + frame_images + knn2_l2f32_kernel (fp16 MFMA, top-8, exact re-rank) + fallback "
+                      "+ match_filter (whole match stage)",
+            "bound": "valu", "achieved": round(issued, 1), "peak": BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
+            "frac": round(issued / BF16_PEAK_TFLOPS, 4), "traffic": None,
+            "algorithmic_tflops_fp32_equiv": round(issued, 1),
+            "avg_launch_ms": iso["match"],
+            "valu_bound": {"distances_per_s_T": round(dists, 3), "peak_distances_per_s_T": round(valu_peak, 3),
+                           "frac": round(dists / valu_peak, 4),
+                           "note": "peak = 1024 SIMDs x 0.25 wave64 VALU instr/cycle x 2.4 GHz x 64 lanes / 8 VALU "
+                                   "per distance (the reference count; the top-8 costs 1 compare per distance "
+                                   "plus 9 VALU when some lane of the wave inserts)"},
+            "note": "achieved = issued fp16 MFMA work (= algorithmic) / isolated stage time; frac against dense fp16"}
+    else:
+        tops = match_ops / iso_match_s / 1e12
+        # knn2_l2u8 is bound by its integer VALU top-2 epilogue (~2.5 VALU per distance), not
+        # by the i8 MFMA: the MFMA fraction is reported beside the VALU-issue one
+        valu_per_dist = 2.5
+        valu_peak = VALU_INSTR_PER_S_PER_GPU * 64 / valu_per_dist / 1e12  # distances/s (T)
+        dists = match_ops / (2.0 * bc.D) / iso_match_s / 1e12
+        result["roofline_match"] = {
+            "kernel": "knn2_l2u8_kernel + match_filter_kernel (whole match stage)", "bound": "valu",
+            "achieved": round(tops, 1), "peak": I8_PEAK_TOPS, "unit": "TOP/s", "frac": round(tops / I8_PEAK_TOPS, 4),
+            "traffic": None, "avg_launch_ms": iso["match"],
+            "valu_bound": {"distances_per_s_T": round(dists, 3), "peak_distances_per_s_T": round(valu_peak, 3),
+                           "frac": round(dists / valu_peak, 4),
+                           "note": "peak = 1024 SIMDs x 0.25 wave64 VALU instr/cycle x 2.4 GHz x 64 lanes / "
+                                   "2.5 VALU per distance (the top-2 epilogue); frac/peak above = i8 MFMA"}}
 
 
 def main():
@@ -542,7 +665,14 @@ def main():
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c2",
                     help="BASELINE workload (c2 = configs[1], the headline line)")
     ap.add_argument("--frames", type=int, default=None, help="frames per GPU (default: the config's)")
-    ap.add_argument("--cpu-sample", type=int, default=None, help="frames in the CPU-baseline sample (0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what takes runs of its own: every GPU stage alone "
+                         "(stage_ms_isolated, the RANSAC / match / isolated-warp rooflines) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned (a seeded sample of the aligned "
+                         "frames, the affines, the consensus and RANSAC results) as DIR/<name>.npy")
+    ap.add_argument("--cpu-sample", type=int, default=None,
+                    help="with --full: frames in the CPU-baseline sample (0: skip)")
     ap.add_argument("--cpu-procs", type=int, default=None,
                     help="worker processes of the CPU baseline (default: the host's usable CPUs, the "
                          "reference's cpu_count()-sized pool as this host runs it)")
@@ -618,14 +748,13 @@ def main():
     def step(timer):
         if ov is None:
             return run_step(inp, cfg, out, timer, world, counts)
-        res = ov.submit(inp, out=out, mark=timer.mark if timer else None)
-        return (res.consensus, res.ransac) if res is not None else None
+        return ov.submit(inp, out=out, mark=timer.mark if timer else None)
 
     def drain(timer):  # the pipelined schedule: finish the slabs still in flight
         if ov is None:
             return None
         res = ov.flush(mark=timer.mark if timer else None)
-        return (res[-1].consensus, res[-1].ransac) if res else None
+        return res[-1] if res else None
 
     for _ in range(args.warmup):
         step(None)
@@ -654,7 +783,9 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    cons, rr = last
+    cons = last.consensus  # `last`: the SlabResult of the last timed step
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last.aligned, last, args.frames, suffix=f"_rank{rank}" if world > 1 else "")
     ms_step = 1e3 * elapsed / args.steps
     total_frames = args.frames * world
     fps = total_frames * args.steps / elapsed
@@ -663,9 +794,6 @@ def main():
     ransac_ms = float(np.mean(timer.elapsed("r0", "r1")))
     n_pts = np.diff(cons.pt_off)
     n_ransac = int((n_pts >= cfg.effective_frame_skip).sum())
-    iso, iso_cons = isolated_stage_ms(inp, cfg, out)
-    iso_pts = np.diff(iso_cons.pt_off)
-    iso_ransac = int((iso_pts >= cfg.effective_frame_skip).sum())
     warp_bytes = 2 * inp.frames.numel() * inp.frames.element_size()  # read + write, algorithmic
     achieved = warp_bytes / (warp_ms * 1e-3) / 1e9
     # the committed PMC pass was taken at the config's own frame count: quote it only there
@@ -706,22 +834,11 @@ def main():
             "descriptor_len": bc.D, "descriptor_dtype": "float32" if bc.descriptor == "f32" else "uint8", "n_kp_global": bc.n_kp_global, "ransac_model": bc.model,
             "ransac_trials": TRIALS, "parallelism": f"frame-sharded x{world}",
         },
-        # RANSAC kernel alone (isolated_stage_ms); the overlapped figure shares the CUs
-        # with the previous step's warp
-        "ransac_hypotheses_per_s_per_gpu": round(iso_ransac * TRIALS / (iso["ransac"] * 1e-3), 1),
-        "roofline_ransac": ransac_roofline(bc.model, iso_cons, cfg, iso["ransac"]),
+        # RANSAC beside the previous step's warp, sharing the CUs with it (the kernel alone:
+        # `ransac_hypotheses_per_s_per_gpu` of a --full run)
         "ransac_hypotheses_per_s_per_gpu_overlapped": round(n_ransac * TRIALS / (ransac_ms * 1e-3), 1),
         "ransac_mean_points": round(float(n_pts.mean()), 2),
         "stage_ms": stage_ms,
-        "stage_ms_isolated": iso,
-        # the warp's own roofline: the same launch alone, median of per-dispatch HIP event
-        # pairs (the timed steps run RANSAC beside it, which `roofline` includes)
-        "roofline_isolated": {"kernel": "warp_plan_kernel + " + ("warp_perspective_u16_kernel"
-                                                               if cfg.ransac_model == "projective" else
-                                                               "warp_affine_u16_kernel"),
-                              "achieved": round(warp_bytes / (iso["warp"] * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS,
-                              "unit": "GB/s", "frac": round(warp_bytes / (iso["warp"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                              "median_launch_ms": iso["warp"]},
         "roofline": {
             "kernel": (f"warp_perspective_u16_kernel<{bc.C}>" if bc.model == "projective"
                        else f"warp_affine_u16_kernel<{bc.C}>"),
@@ -736,52 +853,13 @@ def main():
             "avg_launch_ms": round(warp_ms, 4),
         },
     }
-    # the matcher against its rooflines (the dominant kernel of c5): algorithmic work
-    # 2 * n_tpl * n_q * D per frame.  The float matcher issues one fp16 product per fp32
-    # product (a certified candidate search; exact fp64 re-rank of 2-3 candidates), priced
-    # against fp16 dense (= bf16 dense); its bound is the top-8 selection on VALU, reported
-    # beside it against 8 integer VALU per distance (round 3's reference count, kept so the
-    # fraction compares across rounds)
-    n_q_total = float(inp.q_off_host[-1])
-    match_ops = 2.0 * bc.n_tpl * n_q_total * bc.D
-    iso_match_s = iso["match"] * 1e-3
-    if bc.descriptor == "f32":
-        issued = match_ops / iso_match_s / 1e12
-        dists = match_ops / (2.0 * bc.D) / iso_match_s / 1e12
-        valu_peak = VALU_INSTR_PER_S_PER_GPU * 64 / 8.0 / 1e12
-        result["roofline_match"] = {
-            "kernel": "tpl_stats + frame_images + knn2_l2f32_kernel (fp16 MFMA, top-8, exact re-rank) + fallback "
-                      "+ match_filter (whole match stage)",
-            "bound": "valu", "achieved": round(issued, 1), "peak": BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
-            "frac": round(issued / BF16_PEAK_TFLOPS, 4), "traffic": None,
-            "algorithmic_tflops_fp32_equiv": round(issued, 1),
-            "avg_launch_ms": iso["match"],
-            "valu_bound": {"distances_per_s_T": round(dists, 3), "peak_distances_per_s_T": round(valu_peak, 3),
-                           "frac": round(dists / valu_peak, 4),
-                           "note": "peak = 1024 SIMDs x 0.25 wave64 VALU instr/cycle x 2.4 GHz x 64 lanes / 8 VALU "
-                                   "per distance (the reference count; the top-8 costs 1 compare per distance "
-                                   "plus 9 VALU when some lane of the wave inserts)"},
-            "note": "achieved = issued fp16 MFMA work (= algorithmic) / isolated stage time; frac against dense fp16"}
-    else:
-        tops = match_ops / iso_match_s / 1e12
-        # knn2_l2u8 is bound by its integer VALU top-2 epilogue (~2.5 VALU per distance), not
-        # by the i8 MFMA: the MFMA fraction is reported beside the VALU-issue one
-        valu_per_dist = 2.5
-        valu_peak = VALU_INSTR_PER_S_PER_GPU * 64 / valu_per_dist / 1e12  # distances/s (T)
-        dists = match_ops / (2.0 * bc.D) / iso_match_s / 1e12
-        result["roofline_match"] = {
-            "kernel": "knn2_l2u8_kernel + match_filter_kernel (whole match stage)", "bound": "valu",
-            "achieved": round(tops, 1), "peak": I8_PEAK_TOPS, "unit": "TOP/s", "frac": round(tops / I8_PEAK_TOPS, 4),
-            "traffic": None, "avg_launch_ms": iso["match"],
-            "valu_bound": {"distances_per_s_T": round(dists, 3), "peak_distances_per_s_T": round(valu_peak, 3),
-                           "frac": round(dists / valu_peak, 4),
-                           "note": "peak = 1024 SIMDs x 0.25 wave64 VALU instr/cycle x 2.4 GHz x 64 lanes / "
-                                   "2.5 VALU per distance (the top-2 epilogue); frac/peak above = i8 MFMA"}}
+    if args.full:
+        full_figures(result, bc, inp, cfg, out, warp_bytes)
     if args.e2e:
         result["end_to_end"] = end_to_end(bc, inp, cfg, dev, world)
     if args.detect and bc.C == 1:
         result["with_detection"] = with_detection(inp, cfg, dev, world)
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0:
         result["cpu_baseline"] = cpu_baseline(bc, ks, args.cpu_sample, args.cpu_procs)
         p2 = args.cpu_procs_secondary
         if p2 and p2 != args.cpu_procs:

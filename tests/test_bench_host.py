@@ -90,3 +90,54 @@ def test_spawn_ranks_children_and_exit_code(tmp_path):
         assert bench.spawn_ranks(2, ["fail"]) == 3
     finally:
         bench.__file__ = real
+
+
+def test_sample_elements_is_a_fixed_sorted_sample():
+    """--dump-outputs: a small stack is copied whole, a larger one sampled at the same flat
+    positions in every run (values above 32767 keep their uint16 meaning)."""
+    import numpy as np
+    import torch
+
+    t = torch.from_numpy((np.arange(6 * 50 * 40, dtype=np.int64) * 7 % 65536).astype(np.int32)).to(torch.uint16)
+    t = t.reshape(6, 50, 40)
+    ref = t.reshape(-1).to(torch.int32).numpy()
+    whole = bench.sample_elements(t, n=t.numel())
+    assert whole.dtype == np.float32 and np.array_equal(whole, ref.astype(np.float32)) and whole.max() > 40000
+    a, b = bench.sample_elements(t, n=1000), bench.sample_elements(t.clone(), n=1000)
+    assert a.shape == (1000,) and np.array_equal(a, b)
+    pos = np.sort(np.random.default_rng(bench.DUMP_SAMPLE_SEED).integers(0, t.numel(), 1000, dtype=np.int64))
+    assert np.array_equal(a, ref[pos].astype(np.float32))
+    assert len(np.unique(pos // (50 * 40))) == 6  # every frame is sampled
+
+
+def test_dump_outputs_writes_float_npy_within_the_limit(tmp_path, monkeypatch):
+    import numpy as np
+    import pytest
+    import torch
+    from kcmc_amd import pipeline, stages
+
+    F = 5
+    aligned = torch.arange(F * 8 * 8, dtype=torch.int32).to(torch.uint16).reshape(F, 8, 8)
+    aff = np.tile(np.eye(2, 3), (F, 1, 1))
+    cons = stages.Consensus(np.array([3, 1], np.int32), np.array([5, 4], np.int32),
+                            pt_off=np.arange(F + 1, dtype=np.int32), pt_idx=np.zeros(F, np.int32))
+    rr = stages.RansacResult(torch.full((F, 2, 3), float("nan"), dtype=torch.float64), torch.zeros(F, dtype=torch.uint8),
+                             torch.arange(F, dtype=torch.int32), torch.zeros(F, dtype=torch.int32))
+    res = pipeline.SlabResult(aligned, aff, np.zeros((F, 3)), [2], [2, 4], consensus=cons, ransac=rr)
+    res.extras["f0"] = 0
+    bench.dump_outputs(str(tmp_path / "d"), aligned, res, F)
+    got = {p.name[:-4]: np.load(p) for p in (tmp_path / "d").iterdir()}
+    assert set(got) == {"aligned_sample", "affines", "euclidean", "skipped", "interpolated", "consensus_order",
+                        "consensus_votes", "pt_off", "pt_idx", "ransac_params", "ransac_n_inliers"}
+    assert got["aligned_sample"].dtype == np.float32 and all(a.dtype == np.float64 for k, a in got.items()
+                                                             if k != "aligned_sample")
+    assert np.array_equal(got["aligned_sample"], np.arange(F * 64, dtype=np.float32))
+    assert got["skipped"].tolist() == [0, 0, 1, 0, 0] and got["interpolated"].tolist() == [0, 0, 1, 0, 1]
+    assert np.array_equal(got["affines"], aff) and np.isnan(got["ransac_params"]).all()
+    assert got["consensus_order"].tolist() == [3, 1] and got["ransac_n_inliers"].tolist() == list(range(F))
+    # a list of per-slab stacks (the single-process split) is sampled slab by slab
+    bench.dump_outputs(str(tmp_path / "s"), [aligned[:2], aligned[2:]], res, F, suffix="_x")
+    assert np.array_equal(np.load(tmp_path / "s" / "aligned_sample_x.npy"), got["aligned_sample"])
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1000)
+    with pytest.raises(SystemExit, match="more than"):
+        bench.dump_outputs(str(tmp_path / "big"), aligned, res, F)

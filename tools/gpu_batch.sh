@@ -10,10 +10,10 @@
 #   smoke                 __graft_entry__.smoke() -> <out>/smoke.log
 #   fuzz:<n>:<start>[:<filter>]  tools/debug/fuzz_campaign.py over seeds [start, start + n) -> <out>/fuzz_<filter>.txt
 #   bench:<cfg>[:<tag>][:<args,comma,separated>]
-#                         bench.py --config <cfg> --cpu-sample 0 [args] -> <out>/<cfg>_<tag>.json
+#                         bench.py --full --config <cfg> --cpu-sample 0 [args] -> <out>/<cfg>_<tag>.json
 #   abbench:<lib>:<cfg>:<tag>  the same against KCMC_LIB_PATH=<lib> (tools/ab_build.py) -> <out>/<cfg>_<tag>.json
 #   envbench:<VAR=val>:<cfg>:<tag>[:<args,comma>]  the same with one extra environment variable
-#   cpubench:<cfg>        bench.py --config <cfg> with its CPU baseline -> <out>/<cfg>_cpu.json
+#   cpubench:<cfg>        bench.py --full --config <cfg> (with its CPU baseline) -> <out>/<cfg>_cpu.json
 #   profile:<cfg>         tools/profile_round.sh (bench + rocprofv3 summary + warp PMC) -> <out>/<cfg>/
 #   abpmc:<lib>:<cfg>:<tag>  the warp PMC passes (tools/pmc_warp.sh) against another build -> <out>/pmc_<tag>/
 #   envtrace:<VAR=val>:<cfg>:<tag>  the same with one extra environment variable
@@ -66,20 +66,20 @@ for step in "$@"; do
     bench)
       tag=${b:-1}
       IFS=, read -r -a X <<< "${c:-}"
-      timeout -k 10 300 python bench.py --config "$a" --cpu-sample 0 "${X[@]}" > "$OUT/${a}_$tag.json" \
+      timeout -k 10 300 python bench.py --full --config "$a" --cpu-sample 0 "${X[@]}" > "$OUT/${a}_$tag.json" \
         2>> "$OUT/bench.err" || exit 1
       echo "$a $tag: $(head -c 160 "$OUT/${a}_$tag.json")" ;;
     abbench)  # abbench:<ab/lib.so>:<cfg>:<tag>  the bench against another build of the library
-      KCMC_TEST_ONLY_ALT_LIB=1 KCMC_LIB_PATH="$a" timeout -k 10 300 python bench.py --config "$b" --cpu-sample 0 > "$OUT/${b}_$c.json" \
+      KCMC_TEST_ONLY_ALT_LIB=1 KCMC_LIB_PATH="$a" timeout -k 10 300 python bench.py --full --config "$b" --cpu-sample 0 > "$OUT/${b}_$c.json" \
         2>> "$OUT/bench.err" || exit 1
       echo "$b $c ($a): $(head -c 160 "$OUT/${b}_$c.json")" ;;
     envbench)  # envbench:<VAR=value>:<cfg>:<tag>[:<args,comma>]  the bench with one extra environment variable
       IFS=, read -r -a X <<< "${d:-}"
-      env "$a" timeout -k 10 300 python bench.py --config "$b" --cpu-sample 0 "${X[@]}" > "$OUT/${b}_$c.json" \
+      env "$a" timeout -k 10 300 python bench.py --full --config "$b" --cpu-sample 0 "${X[@]}" > "$OUT/${b}_$c.json" \
         2>> "$OUT/bench.err" || exit 1
       echo "$b $c ($a): $(head -c 160 "$OUT/${b}_$c.json")" ;;
     cpubench)
-      timeout -k 10 400 python bench.py --config "$a" > "$OUT/${a}_cpu.json" 2>> "$OUT/bench.err" || exit 1
+      timeout -k 10 400 python bench.py --full --config "$a" > "$OUT/${a}_cpu.json" 2>> "$OUT/bench.err" || exit 1
       echo "$a cpu: $(head -c 160 "$OUT/${a}_cpu.json")" ;;
     profile)
       bash tools/profile_round.sh "$OUT/$a" --config "$a" || exit 1 ;;
