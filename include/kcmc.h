@@ -18,6 +18,8 @@
  *                             only the O(n_tpl) votes).
  *   kcmc_ransac_rigid      <- _compute_euclidean_affine (VA:288-323), i.e. skimage 0.18.3
  *                             ransac(EuclideanTransform, 2, 2, max_trials, random_state).
+ *   kcmc_ransac_similarity <- the same call with SimilarityTransform (an extension: the
+ *                             reference fits EuclideanTransform only).
  *   kcmc_warp_affine_u16   <- _apply_affine (VA:455-458): cv2.warpAffine(img, M, (W,H),
  *                             INTER_LINEAR), BORDER_CONSTANT 0, classic fixed-point path.
  *
@@ -248,6 +250,22 @@ int kcmc_ransac_rigid(kcmc_ctx* ctx, const double* src_dev, const double* dst_de
                       uint8_t* out_inliers_dev, int32_t* out_n_inliers_dev,
                       int32_t* out_best_trial_dev, kcmc_stream_t stream);
 
+/* K2s: batched similarity RANSAC (rotation, translation and one scale), i.e. skimage 0.18.3
+ * ransac(..., SimilarityTransform, min_samples=2, ...): _umeyama(estimate_scale=True) for
+ * the 2-point hypotheses and for the refit on the inliers.  The same kernel as
+ * kcmc_ransac_rigid (its scorer, selection and early exit), the same parameter list, the
+ * same hypothesis tables (kcmc_ransac_prepare) and the same outputs and NaN conventions:
+ *   out_params_dev   [n_frames, 2, 3] f64  model.params[:2] = [scale * R | t],
+ *                                          translation * spatial_rate
+ * Its parity with skimage rests on an operation-for-operation numpy restatement
+ * (tests/test_similarity_host.py), not on a golden from skimage itself. */
+int kcmc_ransac_similarity(kcmc_ctx* ctx, const double* src_dev, const double* dst_dev,
+                           const int32_t* pt_idx_dev, const int32_t* pt_off_dev, int src_frame_stride,
+                           int n_frames, int max_n, int trials, double residual_threshold,
+                           double spatial_rate, int n_skip, double* out_params_dev,
+                           uint8_t* out_inliers_dev, int32_t* out_n_inliers_dev,
+                           int32_t* out_best_trial_dev, kcmc_stream_t stream);
+
 /* ------------------------------------------------- K2 extension: affine / projective
  * The reference only fits EuclideanTransform (VA:311).  BASELINE configs 3-5 need the
  * other scikit-image 0.18.3 models through the same ransac call (fit.py:621-881):
@@ -256,7 +274,7 @@ int kcmc_ransac_rigid(kcmc_ctx* ctx, const double* src_dev, const double* dst_de
  * with the same seeded sample stream (RandomState(seed).choice(N, min_samples, False)
  * per trial) and skimage's total-least-squares refit on the inliers
  * (_geometric.py:596-703). */
-enum { KCMC_MODEL_EUCLIDEAN = 0, KCMC_MODEL_AFFINE = 1, KCMC_MODEL_PROJECTIVE = 2 };
+enum { KCMC_MODEL_EUCLIDEAN = 0, KCMC_MODEL_AFFINE = 1, KCMC_MODEL_PROJECTIVE = 2, KCMC_MODEL_SIMILARITY = 3 };
 
 /* kcmc_ransac_prepare for min_samples in {2, 3, 4} (2 is kcmc_ransac_prepare itself).
  * Every point count must exceed min_samples (skimage raises otherwise, fit.py:798). */

@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = (
     "kcmc_hypothesis_table",
     "kcmc_ransac_prepare",
     "kcmc_ransac_rigid",
+    "kcmc_ransac_similarity",
     "kcmc_ransac_prepare_samples",
     "kcmc_ransac_model",
     "kcmc_warp_affine_u16",
@@ -59,8 +60,10 @@ EXPORTED_SYMBOLS = (
 KCMC_MODEL_EUCLIDEAN = 0
 KCMC_MODEL_AFFINE = 1
 KCMC_MODEL_PROJECTIVE = 2
-MODEL_IDS = {"euclidean": KCMC_MODEL_EUCLIDEAN, "affine": KCMC_MODEL_AFFINE, "projective": KCMC_MODEL_PROJECTIVE}
-MODEL_MIN_SAMPLES = {"euclidean": 2, "affine": 3, "projective": 4}
+KCMC_MODEL_SIMILARITY = 3
+MODEL_IDS = {"euclidean": KCMC_MODEL_EUCLIDEAN, "affine": KCMC_MODEL_AFFINE, "projective": KCMC_MODEL_PROJECTIVE,
+             "similarity": KCMC_MODEL_SIMILARITY}
+MODEL_MIN_SAMPLES = {"euclidean": 2, "affine": 3, "projective": 4, "similarity": 2}
 
 
 class KcmcLibraryError(RuntimeError):
@@ -108,6 +111,7 @@ _SIGNATURES = {
     "kcmc_hypothesis_table": ([I, I, U32, I, P], I),
     "kcmc_ransac_prepare": ([P, P, I, I, U32], I),
     "kcmc_ransac_rigid": ([P, P, P, P, P, I, I, I, I, D, D, I, P, P, P, P, P], I),
+    "kcmc_ransac_similarity": ([P, P, P, P, P, I, I, I, I, D, D, I, P, P, P, P, P], I),
     "kcmc_ransac_prepare_samples": ([P, I, P, I, I, U32], I),
     "kcmc_ransac_model": ([P, I, P, P, P, P, I, I, I, I, D, D, I, P, P, P, P, P], I),
     "kcmc_warp_affine_u16": ([P, P, P, P, I, I, I, I, I, P], I),

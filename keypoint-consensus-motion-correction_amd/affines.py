@@ -197,3 +197,15 @@ def euclidean_transforms(affines: np.ndarray) -> np.ndarray:
     with np.errstate(invalid="ignore"):  # arccos(a00 > 1) -> NaN, as in the reference
         t[:, 2] = np.arccos(affines[:, 0, 0])
     return t
+
+
+def similarity_transforms(affines: np.ndarray) -> np.ndarray:
+    """The summary of the similarity model's maps [n, 2, 3] = [scale R | t]:
+    [x_translation, y_translation, rotation = atan2(a10, a00), scale = hypot(a00, a10)] per
+    frame (the rotation keeps its sign; euclidean_transforms' arccos(a00) would read the
+    scale into the angle)."""
+    t = np.zeros((affines.shape[0], 4))
+    t[:, :2] = affines[:, :2, 2]
+    t[:, 2] = np.arctan2(affines[:, 1, 0], affines[:, 0, 0])
+    t[:, 3] = np.hypot(affines[:, 0, 0], affines[:, 1, 0])
+    return t

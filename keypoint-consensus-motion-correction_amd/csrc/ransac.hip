@@ -1,4 +1,5 @@
-// K2: batched rigid RANSAC with scikit-image 0.18.3 semantics.
+// K2: batched rigid RANSAC with scikit-image 0.18.3 semantics, and K2s: the same kernel
+// for SimilarityTransform (SCALE = true: rotation, translation and one scale).
 //
 // Reference: VA:288-323 (_compute_euclidean_affine) ->
 //   skimage.measure.ransac((kp_query, kp_template), EuclideanTransform, min_samples=2,
@@ -20,6 +21,14 @@
 // (kcmc_ransac_prepare) -- it depends on N only because every frame reseeds.
 // Refit: rigid Umeyama over the best inlier set (wave 0 alone for N <= 128, workgroup
 // reductions above; the same sums in the same order either way).
+//
+// K2s (kcmc_ransac_similarity): ransac(..., SimilarityTransform, min_samples=2, ...), i.e.
+// _umeyama(estimate_scale=True).  With a = a00 + a11, b = a10 - a01 of the un-normalised
+// covariance sums and v = sum |src_d|^2: a^2 + b^2 = (s1 +- s2)^2 (the sign of det A), so
+// skimage's scale = (S @ d) / var is hypot(a, b) / v and the entries of scale * R are a / v
+// and b / v (no root).  Same hypothesis tables, residual, scoring phases, selection and
+// replay as the rigid model; only the 2-point fit, the refit (one more sum, v over the
+// inliers) and the caller's summary differ.
 #include <cfloat>
 #include <cmath>
 
@@ -36,7 +45,10 @@ struct Model {
   bool ok;
 };
 
-// Closed-form rigid fit of two correspondences (skimage _umeyama, estimate_scale=False).
+// Closed-form rigid fit of two correspondences (skimage _umeyama, estimate_scale=False);
+// SCALE: the similarity fit (estimate_scale=True), c and s hold the entries of scale * R.
+// Every two-term sum commutes, so swapping the two points gives the same model to the bit.
+template <bool SCALE>
 __device__ __forceinline__ Model fit2(double sx0, double sy0, double sx1, double sy1, double dx0, double dy0,
                                       double dx1, double dy1) {
   Model m;
@@ -50,9 +62,15 @@ __device__ __forceinline__ Model fit2(double sx0, double sy0, double sx1, double
   const double a11 = p1 * a1 + q1 * b1;
   const double a = a00 + a11, b = a10 - a01;
   m.ok = !(a == 0.0 && b == 0.0);
-  const double hn = sqrt(a * a + b * b);
-  m.c = a / hn;
-  m.s = b / hn;
+  if (SCALE) {
+    const double v = (a0 * a0 + b0 * b0) + (a1 * a1 + b1 * b1);
+    m.c = a / v;
+    m.s = b / v;
+  } else {
+    const double hn = sqrt(a * a + b * b);
+    m.c = a / hn;
+    m.s = b / hn;
+  }
   m.tx = md0 - (m.c * ms0 - m.s * ms1);
   m.ty = md1 - (m.s * ms0 + m.c * ms1);
   return m;
@@ -122,7 +140,7 @@ __device__ __forceinline__ float score_fast(const Model& m, const Pts& P, int N,
 // (ransac_common.h); invalid trials (NaN S, or 0 inliers with S = inf) never win.
 // LARGE = false handles frames with N <= 128 (one pairwise leaf, fully in registers)
 // and the NaN frames; LARGE = true handles 128 < N <= kMaxN through the split plan.
-template <bool LARGE>
+template <bool LARGE, bool SCALE>
 __device__ __forceinline__ void ransac_rigid_frame(
     int f, const double* __restrict__ src, const double* __restrict__ dst, const int32_t* __restrict__ pt_idx,
     const int32_t* __restrict__ pt_off, int src_stride, const uint32_t* __restrict__ hyp,
@@ -259,7 +277,7 @@ __device__ __forceinline__ void ransac_rigid_frame(
     for (int t = tid; t < T; t += kThreads) {
       const uint32_t pr = H[t];
       const int i = (int)(pr & 0xffffu), j = (int)(pr >> 16);
-      const Model m = fit2(sx[i], sy[i], sx[j], sy[j], dxs[i], dys[i], dxs[j], dys[j]);
+      const Model m = fit2<SCALE>(sx[i], sy[i], sx[j], sy[j], dxs[i], dys[i], dxs[j], dys[j]);
       int v = -1;
       double slo = NAN, shi = NAN;
       Lin32 L;
@@ -283,7 +301,7 @@ __device__ __forceinline__ void ransac_rigid_frame(
         if (tC[t] != INT_MIN) continue;
         const uint32_t pr = H[t];
         const int i = (int)(pr & 0xffffu), j = (int)(pr >> 16);
-        const Model m = fit2(sx[i], sy[i], sx[j], sy[j], dxs[i], dys[i], dxs[j], dys[j]);
+        const Model m = fit2<SCALE>(sx[i], sy[i], sx[j], sy[j], dxs[i], dys[i], dxs[j], dys[j]);
         int cnt = 0;
         const float S32 = score_fast(m, P, N, tq, cnt);
         double slo, shi;
@@ -318,7 +336,7 @@ __device__ __forceinline__ void ransac_rigid_frame(
         need &= need - 1;
         const uint32_t pr = H[tc];
         const int i = (int)(pr & 0xffffu), j = (int)(pr >> 16);
-        const Model m = fit2(sx[i], sy[i], sx[j], sy[j], dxs[i], dys[i], dxs[j], dys[j]);
+        const Model m = fit2<SCALE>(sx[i], sy[i], sx[j], sy[j], dxs[i], dys[i], dxs[j], dys[j]);
         int c = 0;
         double sq = 0.0;
         for (int k = lane; k < N; k += 64) {
@@ -365,7 +383,7 @@ __device__ __forceinline__ void ransac_rigid_frame(
     for (int t = tid; t < T; t += kThreads) {
       const uint32_t pr = H[t];
       const int i = (int)(pr & 0xffffu), j = (int)(pr >> 16);
-      const Model m = fit2(sx[i], sy[i], sx[j], sy[j], dxs[i], dys[i], dxs[j], dys[j]);
+      const Model m = fit2<SCALE>(sx[i], sy[i], sx[j], sy[j], dxs[i], dys[i], dxs[j], dys[j]);
       int cnt = 0;
       double S = NAN;
       if (m.ok) {
@@ -415,7 +433,7 @@ __device__ __forceinline__ void ransac_rigid_frame(
         cand &= cand - 1;
         const uint32_t pr = H[tc];
         const int i = (int)(pr & 0xffffu), j = (int)(pr >> 16);
-        const Model m = fit2(sx[i], sy[i], sx[j], sy[j], dxs[i], dys[i], dxs[j], dys[j]);
+        const Model m = fit2<SCALE>(sx[i], sy[i], sx[j], sy[j], dxs[i], dys[i], dxs[j], dys[j]);
         const double S = wave_pairwise<LARGE>(
             [&](int k) {
               int c = 0;
@@ -487,7 +505,7 @@ __device__ __forceinline__ void ransac_rigid_frame(
   if (best_t >= 0) {
     const uint32_t pr = H[best_t];
     const int i = (int)(pr & 0xffffu), j = (int)(pr >> 16);
-    bm = fit2(sx[i], sy[i], sx[j], sy[j], dxs[i], dys[i], dxs[j], dys[j]);
+    bm = fit2<SCALE>(sx[i], sy[i], sx[j], sy[j], dxs[i], dys[i], dxs[j], dys[j]);
   }
   for (int k = tid; k < N; k += kThreads) {
     int c = 0;
@@ -498,7 +516,7 @@ __device__ __forceinline__ void ransac_rigid_frame(
   }
   __syncthreads();
   // refit on the inliers (skimage fit.py:871-875 -> _umeyama over d[best_inliers])
-  double n_in, ms0, ms1, md0, md1, a00 = 0, a01 = 0, a10 = 0, a11 = 0;
+  double n_in, ms0, ms1, md0, md1, a00 = 0, a01 = 0, a10 = 0, a11 = 0, vs = 0;
   if (!LARGE) {
     // N <= 128: wave 0 alone, with no barrier.  Lane l holds points l and l + 64, the
     // points threads l and l + 64 hold in the workgroup form below; each half goes through
@@ -519,7 +537,7 @@ __device__ __forceinline__ void ransac_rigid_frame(
     ms1 = half_sums(i0 ? 0.0 + sy[lane] : 0.0, i1 ? 0.0 + sy[k1] : 0.0) / n_in;
     md0 = half_sums(i0 ? 0.0 + dxs[lane] : 0.0, i1 ? 0.0 + dxs[k1] : 0.0) / n_in;
     md1 = half_sums(i0 ? 0.0 + dys[lane] : 0.0, i1 ? 0.0 + dys[k1] : 0.0) / n_in;
-    double b[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+    double b[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, bv[2] = {0, 0};
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int k = h ? k1 : lane;
@@ -530,12 +548,14 @@ __device__ __forceinline__ void ransac_rigid_frame(
         b[h][1] = 0.0 + v0 * u1;
         b[h][2] = 0.0 + v1 * u0;
         b[h][3] = 0.0 + v1 * u1;
+        if (SCALE) bv[h] = 0.0 + (u0 * u0 + u1 * u1);
       }
     }
     a00 = half_sums(b[0][0], b[1][0]);
     a01 = half_sums(b[0][1], b[1][1]);
     a10 = half_sums(b[0][2], b[1][2]);
     a11 = half_sums(b[0][3], b[1][3]);
+    if (SCALE) vs = half_sums(bv[0], bv[1]);
   } else {
     double s0 = 0, s1 = 0, s2 = 0, s3 = 0, cntd = 0;
     for (int k = tid; k < N; k += kThreads)
@@ -559,17 +579,19 @@ __device__ __forceinline__ void ransac_rigid_frame(
         a01 += v0 * u1;
         a10 += v1 * u0;
         a11 += v1 * u1;
+        if (SCALE) vs += u0 * u0 + u1 * u1;
       }
     a00 = block_sum(a00, red);
     a01 = block_sum(a01, red);
     a10 = block_sum(a10, red);
     a11 = block_sum(a11, red);
+    if (SCALE) vs = block_sum(vs, red);
   }
   if (tid == 0) {
     double* o = out_params + 6 * (size_t)f;
     const double a = a00 + a11, b = a10 - a01;
     if (n_in > 0.0 && !(a == 0.0 && b == 0.0)) {
-      const double hn = sqrt(a * a + b * b);
+      const double hn = SCALE ? vs : sqrt(a * a + b * b);
       const double c = a / hn, s = b / hn;
       o[0] = c;
       o[1] = -s;
@@ -588,7 +610,7 @@ __device__ __forceinline__ void ransac_rigid_frame(
 
 // Workgroup g scores frames g, g + grid, ... (the product launches one workgroup per frame;
 // narrower grids measured slower beside the warp).
-template <bool LARGE>
+template <bool LARGE, bool SCALE>
 __global__ __launch_bounds__(kThreads, 4) void ransac_rigid_kernel(
     int n_frames, const double* __restrict__ src, const double* __restrict__ dst, const int32_t* __restrict__ pt_idx,
     const int32_t* __restrict__ pt_off, int src_stride, const uint32_t* __restrict__ hyp,
@@ -596,8 +618,8 @@ __global__ __launch_bounds__(kThreads, 4) void ransac_rigid_kernel(
     int T, double thresh, double tq, double rate, int n_skip, double* __restrict__ out_params,
     uint8_t* __restrict__ out_inl, int32_t* __restrict__ out_nin, int32_t* __restrict__ out_best) {
   for (int f = blockIdx.x; f < n_frames; f += gridDim.x) {
-    ransac_rigid_frame<LARGE>(f, src, dst, pt_idx, pt_off, src_stride, hyp, hyp_off, hyp_off_len, T, thresh, tq, rate,
-                              n_skip, out_params, out_inl, out_nin, out_best);
+    ransac_rigid_frame<LARGE, SCALE>(f, src, dst, pt_idx, pt_off, src_stride, hyp, hyp_off, hyp_off_len, T, thresh, tq,
+                                     rate, n_skip, out_params, out_inl, out_nin, out_best);
     __syncthreads();  // the frame's LDS is free for the next one
   }
 }
@@ -607,20 +629,22 @@ __global__ __launch_bounds__(kThreads, 4) void ransac_rigid_kernel(
 
 using namespace kcmc;
 
+template <bool SCALE>
 static int ransac_rigid_impl(kcmc_ctx* ctx, const double* src, const double* dst, const int32_t* pt_idx,
                                  const int32_t* pt_off, int src_frame_stride, int n_frames, int max_n, int trials,
                                  double thresh, double rate, int n_skip, double* out_params, uint8_t* out_inliers,
                                  int32_t* out_n_inliers, int32_t* out_best_trial, int max_workgroups, kcmc_stream_t stream) {
-  if (!ctx) return fail(KCMC_EINVAL, "kcmc_ransac_rigid: ctx is NULL");
-  if (n_frames < 0 || max_n < 0 || trials < 1) return fail(KCMC_EINVAL, "kcmc_ransac_rigid: bad sizes");
+  const char* const who = SCALE ? "kcmc_ransac_similarity: " : "kcmc_ransac_rigid: ";  // failures only
+  if (!ctx) return fail(KCMC_EINVAL, std::string(who) + "ctx is NULL");
+  if (n_frames < 0 || max_n < 0 || trials < 1) return fail(KCMC_EINVAL, std::string(who) + "bad sizes");
   if (n_frames == 0) return KCMC_OK;
   if (!pt_off || !out_params || !out_n_inliers || !out_best_trial || (max_n > 0 && (!src || !dst || !out_inliers)))
-    return fail(KCMC_EINVAL, "kcmc_ransac_rigid: NULL pointer");
-  if (max_n > kMaxN) return fail(KCMC_EUNSUPPORTED, "kcmc_ransac_rigid: max_n > 4096 points per frame");
-  if (pt_idx && src_frame_stride <= 0) return fail(KCMC_EINVAL, "kcmc_ransac_rigid: src_frame_stride must be > 0");
+    return fail(KCMC_EINVAL, std::string(who) + "NULL pointer");
+  if (max_n > kMaxN) return fail(KCMC_EUNSUPPORTED, std::string(who) + "max_n > 4096 points per frame");
+  if (pt_idx && src_frame_stride <= 0) return fail(KCMC_EINVAL, std::string(who) + "src_frame_stride must be > 0");
   const int need = max_n < 3 ? 3 : max_n;
   if (!ctx->hyp || ctx->hyp_trials != trials)
-    return fail(KCMC_EINVAL, "kcmc_ransac_rigid: hypothesis tables not prepared for trials=" +
+    return fail(KCMC_EINVAL, std::string(who) + "hypothesis tables not prepared for trials=" +
                                  std::to_string(trials) + " (call kcmc_ransac_prepare)");
   const int n_small = need < 128 ? need : 128;
   const size_t wvals = (size_t)kThreads / 64 * 128 * sizeof(double);
@@ -631,17 +655,17 @@ static int ransac_rigid_impl(kcmc_ctx* ctx, const double* src, const double* dst
                            (size_t)kMaxStack * kThreads * sizeof(double) + wvals + (size_t)need + 16;
   const double tq = inlier_bound(thresh);
   if ((max_n > 128 ? lds_large : lds_small) > 150 * 1024)
-    return fail(KCMC_EUNSUPPORTED, "kcmc_ransac_rigid: max_n/trials exceed the LDS budget");
+    return fail(KCMC_EUNSUPPORTED, std::string(who) + "max_n/trials exceed the LDS budget");
   hipStream_t s = (hipStream_t)stream;
   const unsigned grid = (unsigned)(max_workgroups > 0 && max_workgroups < n_frames ? max_workgroups : n_frames);
-  hipLaunchKernelGGL(ransac_rigid_kernel<false>, dim3(grid), dim3(kThreads), lds_small, s, n_frames, src, dst, pt_idx,
-                     pt_off, src_frame_stride, ctx->hyp, ctx->hyp_off, ctx->hyp_off_len, trials, thresh, tq, rate, n_skip,
-                     out_params, out_inliers, out_n_inliers, out_best_trial);
+  hipLaunchKernelGGL((ransac_rigid_kernel<false, SCALE>), dim3(grid), dim3(kThreads), lds_small, s, n_frames, src, dst,
+                     pt_idx, pt_off, src_frame_stride, ctx->hyp, ctx->hyp_off, ctx->hyp_off_len, trials, thresh, tq, rate,
+                     n_skip, out_params, out_inliers, out_n_inliers, out_best_trial);
   KCMC_TRY(launch_check("ransac_rigid_kernel<small>"));
   if (max_n > 128) {
-    hipLaunchKernelGGL(ransac_rigid_kernel<true>, dim3(grid), dim3(kThreads), lds_large, s, n_frames, src, dst, pt_idx,
-                       pt_off, src_frame_stride, ctx->hyp, ctx->hyp_off, ctx->hyp_off_len, trials, thresh, tq, rate, n_skip,
-                       out_params, out_inliers, out_n_inliers, out_best_trial);
+    hipLaunchKernelGGL((ransac_rigid_kernel<true, SCALE>), dim3(grid), dim3(kThreads), lds_large, s, n_frames, src, dst,
+                       pt_idx, pt_off, src_frame_stride, ctx->hyp, ctx->hyp_off, ctx->hyp_off_len, trials, thresh, tq, rate,
+                       n_skip, out_params, out_inliers, out_n_inliers, out_best_trial);
     KCMC_TRY(launch_check("ransac_rigid_kernel<large>"));
   }
   return KCMC_OK;
@@ -651,5 +675,13 @@ extern "C" int kcmc_ransac_rigid(kcmc_ctx* ctx, const double* src, const double*
                                  const int32_t* pt_off, int src_frame_stride, int n_frames, int max_n, int trials,
                                  double thresh, double rate, int n_skip, double* out_params, uint8_t* out_inliers,
                                  int32_t* out_n_inliers, int32_t* out_best_trial, kcmc_stream_t stream) {
-  return ransac_rigid_impl(ctx, src, dst, pt_idx, pt_off, src_frame_stride, n_frames, max_n, trials, thresh, rate, n_skip, out_params, out_inliers, out_n_inliers, out_best_trial, 0, stream);
+  return ransac_rigid_impl<false>(ctx, src, dst, pt_idx, pt_off, src_frame_stride, n_frames, max_n, trials, thresh, rate, n_skip, out_params, out_inliers, out_n_inliers, out_best_trial, 0, stream);
+}
+
+extern "C" int kcmc_ransac_similarity(kcmc_ctx* ctx, const double* src, const double* dst, const int32_t* pt_idx,
+                                      const int32_t* pt_off, int src_frame_stride, int n_frames, int max_n, int trials,
+                                      double thresh, double rate, int n_skip, double* out_params, uint8_t* out_inliers,
+                                      int32_t* out_n_inliers, int32_t* out_best_trial, kcmc_stream_t stream) {
+  return ransac_rigid_impl<true>(ctx, src, dst, pt_idx, pt_off, src_frame_stride, n_frames, max_n, trials, thresh, rate,
+                                 n_skip, out_params, out_inliers, out_n_inliers, out_best_trial, 0, stream);
 }

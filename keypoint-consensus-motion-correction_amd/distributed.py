@@ -174,7 +174,8 @@ def align_sharded(inp: _pl.SlabInputs, cfg: _pl.AlignConfig, group=None, impl: S
     local, skipped, interpolated = _aff.fill_gaps_slab(params.cpu().numpy(), f0, prev, nxt,
                                                        lerp=cfg.ransac_model == "euclidean")
     aligned = impl.warp(inp.frames, local)
-    res = _pl.SlabResult(aligned, local, _aff.euclidean_transforms(local), skipped, interpolated, consensus=cons)
+    res = _pl.SlabResult(aligned, local, _pl.summary_transforms(local, cfg.ransac_model), skipped, interpolated,
+                         consensus=cons)
     res.extras["f0"] = f0
     return res
 

@@ -39,7 +39,7 @@ class AlignConfig:
     frame_downsample_rate: int = 1      # max(1, frame_rate // FRAME_SAMPLE_RATE)
     # Extension (BASELINE configs 3-5): the skimage model class RANSAC fits.  The
     # reference always uses "euclidean" (EuclideanTransform, VA:311).
-    ransac_model: str = "euclidean"     # "euclidean" | "affine" | "projective"
+    ransac_model: str = "euclidean"     # "euclidean" | "similarity" | "affine" | "projective"
     # Opt-in (not the reference's matcher): BFMatcher norm, "l2" (the reference's
     # cv2.BFMatcher() default, VA:194) or "hamming" (NORM_HAMMING for binary descriptors).
     match_norm: str = "l2"
@@ -50,7 +50,7 @@ class AlignConfig:
         for the extension models (skimage needs min_samples < N, fit.py:798)."""
         if self.ransac_model == "euclidean":
             return self.n_kp_frame_skip
-        return max(self.n_kp_frame_skip, {"affine": 3, "projective": 4}[self.ransac_model] + 1)
+        return max(self.n_kp_frame_skip, {"similarity": 2, "affine": 3, "projective": 4}[self.ransac_model] + 1)
 
 
 @dataclass
@@ -71,7 +71,7 @@ class SlabInputs:
 class SlabResult:
     aligned: torch.Tensor
     affines: np.ndarray           # [S*rate, 2, 3] after interpolation (VA:143-144)
-    euclidean: np.ndarray         # [S*rate, 3]
+    euclidean: np.ndarray         # [S*rate, 3] ([S*rate, 4] with the scale for "similarity")
     skipped: List[int]
     interpolated: List[int]
     match: Optional[stages.MatchResult] = None
@@ -192,7 +192,8 @@ def prepare_ransac(device, cfg: AlignConfig) -> None:
 def _check_point_counts(cons: stages.Consensus, cfg: AlignConfig) -> None:
     """skimage raises when a frame is not skipped but has N <= min_samples (fit.py:798-799);
     only reachable when N_KP_FRAME_SKIP <= min_samples (the host then reads pt_off)."""
-    ms = {"euclidean": cfg.ransac_min_samples, "affine": 3, "projective": 4}[cfg.ransac_model]
+    ms = {"euclidean": cfg.ransac_min_samples, "similarity": cfg.ransac_min_samples, "affine": 3,
+          "projective": 4}[cfg.ransac_model]
     skip = cfg.effective_frame_skip
     if skip > ms:
         return
@@ -205,14 +206,16 @@ def ransac_stage(match: stages.MatchResult, kp_tpl: torch.Tensor, cons: stages.C
                  cfg: AlignConfig, lists_dev: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                  stream: Optional[int] = None, max_n: Optional[int] = None) -> stages.RansacResult:
     """VA:137-142: RANSAC of every frame's consensus points (src = the frame's matched
-    keypoints, dst = template keypoints).  params [F, 2, 3] for the euclidean and
-    affine models (model.params[:2], like VA:319), [F, 3, 3] for the projective one.
+    keypoints, dst = template keypoints).  params [F, 2, 3] for the euclidean, similarity
+    and affine models (model.params[:2], like VA:319), [F, 3, 3] for the projective one.
     Device point lists (device_consensus / lookup_stage) run with the tables of every
     count up to n_kp_global; host lists (consensus_stage) are uploaded first unless
     ``lists_dev`` holds them already."""
     if cfg.ransac_model == "euclidean" and cfg.ransac_min_samples != 2:
         # every path (host or device lists) fits EuclideanTransform's 2-point model
         raise ValueError("rigid RANSAC uses min_samples=2 (EuclideanTransform, VA:312)")
+    if cfg.ransac_model == "similarity" and cfg.ransac_min_samples != 2:
+        raise ValueError("similarity RANSAC uses min_samples=2")
     dev = kp_tpl.device
     F, n_tpl = match.kp_ordered.shape[:2]
     src = match.kp_ordered.view(F * n_tpl, 2)
@@ -232,6 +235,12 @@ def ransac_stage(match: stages.MatchResult, kp_tpl: torch.Tensor, cons: stages.C
                                        src_frame_stride=n_tpl, trials=cfg.ransac_trials,
                                        residual_threshold=cfg.ransac_threshold, spatial_rate=cfg.spatial_rate,
                                        n_skip=cfg.n_kp_frame_skip, seed=cfg.seed, min_samples=cfg.ransac_min_samples)
+        if cfg.ransac_model == "similarity":
+            return stages.ransac_similarity(src, kp_tpl, pt_off, cons.pt_off, pt_idx=pt_idx,
+                                            src_frame_stride=n_tpl, trials=cfg.ransac_trials,
+                                            residual_threshold=cfg.ransac_threshold, spatial_rate=cfg.spatial_rate,
+                                            n_skip=cfg.effective_frame_skip, seed=cfg.seed,
+                                            min_samples=cfg.ransac_min_samples)
         rr = stages.ransac_model(src, kp_tpl, pt_off, cons.pt_off, model=cfg.ransac_model,
                                  pt_idx=pt_idx, src_frame_stride=n_tpl, trials=cfg.ransac_trials,
                                  residual_threshold=cfg.ransac_threshold, spatial_rate=cfg.spatial_rate,
@@ -241,21 +250,30 @@ def ransac_stage(match: stages.MatchResult, kp_tpl: torch.Tensor, cons: stages.C
     return rr
 
 
+def summary_transforms(affines: np.ndarray, model: str) -> np.ndarray:
+    """The per-frame summary align_images returns second: the reference's (tx, ty, rotation)
+    (VA:440-453), or (tx, ty, rotation, scale) for the similarity model."""
+    if model == "similarity":
+        return _aff.similarity_transforms(affines)
+    return _aff.euclidean_transforms(affines)
+
+
 def postprocess_affines(params_host: np.ndarray, cfg: AlignConfig):
-    """VA:143-145 on the host: NaN-pad, interpolate, Euclidean summary.  The
+    """VA:143-145 on the host: NaN-pad, interpolate, Euclidean summary ([n, 4] with the
+    scale for the similarity model).  The
     reference's rotation-angle lerp (VA:409-437) assumes rigid matrices; the extension
     models interpolate their gaps entry-wise linearly instead.  Every frame with a model
     and no temporal downsampling (the common case) is one copy."""
     a = np.asarray(params_host)
     if int(cfg.frame_downsample_rate) == 1 and not _aff._nan_rows(a).any():
         affines = np.array(a, dtype=np.float64, copy=True)
-        return affines, [], [], _aff.euclidean_transforms(affines)
+        return affines, [], [], summary_transforms(affines, cfg.ransac_model)
     affines, skipped = _aff.process_affines(a, cfg.frame_downsample_rate)
     if cfg.ransac_model == "euclidean":
         affines, interpolated = _aff.interpolate_affines(affines)
     else:
         affines, interpolated = _aff.interpolate_linear(affines)
-    return affines, skipped, interpolated, _aff.euclidean_transforms(affines)
+    return affines, skipped, interpolated, summary_transforms(affines, cfg.ransac_model)
 
 
 def warp_frames(frames: torch.Tensor, maps: torch.Tensor, out: Optional[torch.Tensor] = None,
@@ -688,7 +706,7 @@ class OverlappedSlabs:
             prev, nxt = neighbours(bounds, self.counts, self._rank)
             local, skipped, interpolated = _aff.fill_gaps_slab(params, p.f0, prev, nxt,
                                                                lerp=self.cfg.ransac_model == "euclidean")
-            affines, eu = local, _aff.euclidean_transforms(local)
+            affines, eu = local, summary_transforms(local, self.cfg.ransac_model)
         else:
             affines, skipped, interpolated, eu = postprocess_affines(params, self.cfg)
             local = np.asarray(affines[:n], dtype=np.float64)

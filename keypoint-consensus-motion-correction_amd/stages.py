@@ -437,25 +437,10 @@ class RansacResult:
     best_trial: torch.Tensor   # [F] i32 (-1: none)
 
 
-def ransac_rigid(
-    src: torch.Tensor,
-    dst: torch.Tensor,
-    pt_off: torch.Tensor,
-    pt_off_host: np.ndarray,
-    pt_idx: Optional[torch.Tensor] = None,
-    src_frame_stride: int = 0,
-    trials: int = 1000,
-    residual_threshold: float = 2.0,
-    spatial_rate: float = 1.0,
-    n_skip: int = 3,
-    seed: int = 42,
-    min_samples: int = 2,
-) -> RansacResult:
-    """skimage ransac(EuclideanTransform) per frame (VA:288-323), all frames in one launch.
-
-    With ``pt_idx``: point k of frame f is src[f*src_frame_stride + pt_idx[k]] /
-    dst[pt_idx[k]] (src = kp_ordered [F*n_tpl, 2], dst = template keypoints).
-    """
+def _ransac_two_point(entry: str, what: str, src, dst, pt_off, pt_off_host, pt_idx, src_frame_stride, trials,
+                      residual_threshold, spatial_rate, n_skip, seed, min_samples) -> RansacResult:
+    """The 2-sample models' launch (C entry ``entry``: kcmc_ransac_rigid / _similarity): checks,
+    the hypothesis tables of the frames' point counts, one launch over every frame."""
     dev = _device_of(src)
     _require(src, "src", torch.float64, dev, 2)
     _require(dst, "dst", torch.float64, dev, 2)
@@ -463,7 +448,7 @@ def ransac_rigid(
     if pt_idx is not None:
         _require(pt_idx, "pt_idx", torch.int32, dev, 1)
     if min_samples != 2:
-        raise ValueError("rigid RANSAC uses min_samples=2 (EuclideanTransform, VA:312)")
+        raise ValueError(what)
     F = pt_off.numel() - 1
     pt_off_host = np.asarray(pt_off_host)
     _check_offsets(pt_off_host, F)
@@ -487,11 +472,57 @@ def ransac_rigid(
     n_run = np.unique(ns[ns >= max(int(n_skip), 3)]).astype(np.int32)
     _lib.check(L.kcmc_ransac_prepare(ctx.handle, _np_ptr(n_run), int(n_run.size), int(trials),
                                      int(seed) & 0xFFFFFFFF))
-    _lib.check(L.kcmc_ransac_rigid(
+    _lib.check(getattr(L, entry)(
         ctx.handle, _ptr(src), _ptr(dst), _ptr(pt_idx), _ptr(pt_off), int(src_frame_stride), F, max_n, int(trials),
         float(residual_threshold), float(spatial_rate), int(n_skip), _ptr(res.params), _ptr(res.inliers),
         _ptr(res.n_inliers), _ptr(res.best_trial), _stream(dev)))
     return res
+
+
+def ransac_rigid(
+    src: torch.Tensor,
+    dst: torch.Tensor,
+    pt_off: torch.Tensor,
+    pt_off_host: np.ndarray,
+    pt_idx: Optional[torch.Tensor] = None,
+    src_frame_stride: int = 0,
+    trials: int = 1000,
+    residual_threshold: float = 2.0,
+    spatial_rate: float = 1.0,
+    n_skip: int = 3,
+    seed: int = 42,
+    min_samples: int = 2,
+) -> RansacResult:
+    """skimage ransac(EuclideanTransform) per frame (VA:288-323), all frames in one launch.
+
+    With ``pt_idx``: point k of frame f is src[f*src_frame_stride + pt_idx[k]] /
+    dst[pt_idx[k]] (src = kp_ordered [F*n_tpl, 2], dst = template keypoints).
+    """
+    return _ransac_two_point("kcmc_ransac_rigid", "rigid RANSAC uses min_samples=2 (EuclideanTransform, VA:312)",
+                             src, dst, pt_off, pt_off_host, pt_idx, src_frame_stride, trials, residual_threshold,
+                             spatial_rate, n_skip, seed, min_samples)
+
+
+def ransac_similarity(
+    src: torch.Tensor,
+    dst: torch.Tensor,
+    pt_off: torch.Tensor,
+    pt_off_host: np.ndarray,
+    pt_idx: Optional[torch.Tensor] = None,
+    src_frame_stride: int = 0,
+    trials: int = 1000,
+    residual_threshold: float = 2.0,
+    spatial_rate: float = 1.0,
+    n_skip: int = 3,
+    seed: int = 42,
+    min_samples: int = 2,
+) -> RansacResult:
+    """skimage ransac(SimilarityTransform, min_samples=2) per frame, all frames in one launch
+    (K2s: the rigid kernel with the scale estimated, csrc/ransac.hip); arguments, addressing
+    forms, skip / NaN conventions and result as ransac_rigid, params [F, 2, 3] = [scale R | t]."""
+    return _ransac_two_point("kcmc_ransac_similarity", "similarity RANSAC uses min_samples=2", src, dst, pt_off,
+                             pt_off_host, pt_idx, src_frame_stride, trials, residual_threshold, spatial_rate, n_skip,
+                             seed, min_samples)
 
 
 def ransac_model(
@@ -515,7 +546,8 @@ def ransac_model(
     Frames with n_skip <= N <= min_samples raise ValueError like skimage
     (fit.py:798-799); frames with N < n_skip get NaN (VA:306-307)."""
     if model not in ("affine", "projective"):
-        raise ValueError(f"model must be 'affine' or 'projective' (got {model!r}); rigid: ransac_rigid")
+        raise ValueError(f"model must be 'affine' or 'projective' (got {model!r}); rigid: ransac_rigid, "
+                         "similarity: ransac_similarity")
     dev = _device_of(src)
     _require(src, "src", torch.float64, dev, 2)
     _require(dst, "dst", torch.float64, dev, 2)
@@ -581,13 +613,14 @@ def ransac_lists(model: str, src: torch.Tensor, dst: torch.Tensor, pt_off: torch
     """RANSAC of every frame on device point lists whose sizes the host does not know
     (the device consensus lookup): max_n bounds every frame's point count (n_kp_global) and
     the tables of every count in [n_skip, max_n] must be ready (ransac_prepare_range).
-    params [F, 2, 3] (euclidean) or [F, 3, 3] (affine / projective), as ransac_rigid /
-    ransac_model."""
+    params [F, 2, 3] (euclidean, similarity) or [F, 3, 3] (affine / projective), as
+    ransac_rigid / ransac_similarity / ransac_model."""
     dev = _device_of(src)
     F = pt_off.numel() - 1
     P = pt_idx.numel()
     res = RansacResult(
-        params=torch.empty((F, 2, 3) if model == "euclidean" else (F, 3, 3), dtype=torch.float64, device=dev),
+        params=torch.empty((F, 2, 3) if model in ("euclidean", "similarity") else (F, 3, 3), dtype=torch.float64,
+                           device=dev),
         inliers=torch.empty((max(P, 1),), dtype=torch.uint8, device=dev),
         n_inliers=torch.empty((F,), dtype=torch.int32, device=dev),
         best_trial=torch.empty((F,), dtype=torch.int32, device=dev),
@@ -597,8 +630,9 @@ def ransac_lists(model: str, src: torch.Tensor, dst: torch.Tensor, pt_off: torch
     L = _lib.load()
     ctx = _ctx(dev).handle
     st = _stream(dev, stream)
-    if model == "euclidean":
-        _lib.check(L.kcmc_ransac_rigid(
+    if model in ("euclidean", "similarity"):
+        entry = L.kcmc_ransac_rigid if model == "euclidean" else L.kcmc_ransac_similarity
+        _lib.check(entry(
             ctx, _ptr(src), _ptr(dst), _ptr(pt_idx), _ptr(pt_off), int(src_frame_stride), F, int(max_n), int(trials),
             float(residual_threshold), float(spatial_rate), int(n_skip), _ptr(res.params), _ptr(res.inliers),
             _ptr(res.n_inliers), _ptr(res.best_trial), st))

@@ -27,16 +27,20 @@ class KeypointSet:
     kp_q: np.ndarray        # [P, 2] f64, CSR over frames
     des_q: np.ndarray       # [P, D] u8
     q_off: np.ndarray       # [F+1] i32
-    gt: np.ndarray          # [F, 2, 3] frame->template rigid maps used to place the points
+    gt: np.ndarray          # [F, 2, 3] ([F, 3, 3]: projective) frame->template maps used to place the points
 
 
 def ground_truth(rng: np.random.Generator, model: str, jitter: float, rot_deg: float,
                  size_hw: Tuple[int, int]) -> np.ndarray:
     """A frame -> template map (SURVEY 8d): rigid jitter N(0, jitter px), N(0, rot_deg);
-    "affine" adds +-1 % scale/shear; "projective" adds perspective terms ~1e-5 / px
-    (scaled to the frame size) and is returned as [3, 3]."""
+    "similarity" scales the rotation by a per-frame factor within +-1 % of 1; "affine" adds
+    +-1 % scale/shear; "projective" adds perspective terms ~1e-5 / px (scaled to the frame
+    size) and is returned as [3, 3]."""
     A = rigid(np.deg2rad(rng.normal(0, rot_deg)), rng.normal(0, jitter), rng.normal(0, jitter))
     if model == "euclidean":
+        return A
+    if model == "similarity":
+        A[:, :2] *= 1.0 + rng.uniform(-0.01, 0.01)
         return A
     A[:, :2] = A[:, :2] @ (np.eye(2) + rng.uniform(-0.01, 0.01, (2, 2)))
     if model == "affine":

@@ -119,7 +119,9 @@ class VideoAligner:
     # run on the first device.
     DEVICE: Optional[int] = None
     # New (extension, BASELINE configs 3-5): the skimage model class RANSAC fits --
-    # "euclidean" (the reference's EuclideanTransform, VA:311), "affine"
+    # "euclidean" (the reference's EuclideanTransform, VA:311), "similarity"
+    # (SimilarityTransform, min_samples 2: rigid plus one scale; the second return value of
+    # align_images / align_keypoints is then [n, 4] = (tx, ty, rotation, scale)), "affine"
     # (AffineTransform, min_samples 3) or "projective" (ProjectiveTransform, min_samples 4,
     # frames warped with warpPerspective).
     RANSAC_MODEL = "euclidean"
@@ -185,7 +187,8 @@ class VideoAligner:
         """Register a uint16 stack [frames, x, y] to a template frame (VA:57-158).
 
         Returns (aligned_imgs, euclidean_transforms [n, 3] = (tx, ty, rotation),
-        skipped_idxs).  A device tensor input yields a device tensor output.
+        skipped_idxs); with RANSAC_MODEL = "similarity" the transforms are [n, 4] = (tx, ty,
+        rotation, scale).  A device tensor input yields a device tensor output.
         """
         self.logger.info(f"aligning {len(images)} frames with n_kp_global: {n_kp_global} and {detector_algorithm}")
         if not 0 <= self.TEMPLATE_FRAME_LOC <= 1:
@@ -468,13 +471,23 @@ class VideoAligner:
     def _compute_euclidean_affine(cls, kp_template: np.ndarray, kp_query: np.ndarray,
                                   spatial_downsample_rate: Union[float, int]) -> Optional[np.ndarray]:
         """VA:288-323 for one frame: seeded rigid RANSAC on the GPU (NaN on failure)."""
+        return cls._compute_frame_affine(stages.ransac_rigid, kp_template, kp_query, spatial_downsample_rate)
+
+    @classmethod
+    def _compute_similarity_affine(cls, kp_template: np.ndarray, kp_query: np.ndarray,
+                                   spatial_downsample_rate: Union[float, int]) -> Optional[np.ndarray]:
+        """_compute_euclidean_affine with SimilarityTransform: [scale R | t] for one frame."""
+        return cls._compute_frame_affine(stages.ransac_similarity, kp_template, kp_query, spatial_downsample_rate)
+
+    @classmethod
+    def _compute_frame_affine(cls, ransac, kp_template, kp_query, spatial_downsample_rate):
         kp_query = np.asarray(kp_query, dtype=np.float64).reshape(-1, 2)
         kp_template = np.asarray(kp_template, dtype=np.float64).reshape(-1, 2)
         if len(kp_query) < cls.N_KP_FRAME_SKIP:
             return np.full((2, 3), np.nan)
         dev = cls._device()
         off = np.array([0, len(kp_query)], np.int32)
-        r = stages.ransac_rigid(
+        r = ransac(
             torch.from_numpy(np.ascontiguousarray(kp_query)).to(dev),
             torch.from_numpy(np.ascontiguousarray(kp_template)).to(dev),
             torch.from_numpy(off).to(dev), off, trials=cls.RANSAC_MAX_TRIALS,
