@@ -22,6 +22,9 @@
  *                             reference fits EuclideanTransform only).
  *   kcmc_warp_affine_u16   <- _apply_affine (VA:455-458): cv2.warpAffine(img, M, (W,H),
  *                             INTER_LINEAR), BORDER_CONSTANT 0, classic fixed-point path.
+ *   kcmc_stack_sum_u16 / kcmc_frame_stats_u16  <- nothing in the reference (an extension):
+ *                             the mean image of the aligned stack and every frame's
+ *                             correlation moments with it.
  *
  * Conventions
  *   - Plain pointers and sizes only.  Pointers named *_dev are device (HBM) pointers
@@ -356,6 +359,28 @@ int kcmc_orb_detect(kcmc_ctx* ctx, const uint8_t* frames_dev, int n_frames, int 
  * unless |2 dst_w - W| <= 2 and |2 dst_h - H| <= 2. */
 int kcmc_pyr_down_u8(kcmc_ctx* ctx, const uint8_t* src_dev, int n_frames, int H, int W, uint8_t* dst_dev,
                      int dst_h, int dst_w, kcmc_stream_t stream);
+
+/* ------------------------------------------------ q1: registration quality metrics
+ * Two streaming reductions of a grayscale uint16 stack, exact in 64-bit integers (the
+ * results do not depend on the order in which workgroups finish).  Asynchronous on
+ * `stream`, capturable, no allocation; each zeroes its own output first.
+ *
+ * out_sum_dev [n_px] i64 = the per-pixel sum over the frames f with sel_dev[f] != 0
+ * (sel_dev [n_frames] u8; NULL = every frame) of frames_dev [n_frames, n_px] u16.  Any
+ * n_frames, n_px and alignment of frames_dev; the 16-byte path needs n_px % 8 == 0 and a
+ * 16-byte aligned frames_dev. */
+int kcmc_stack_sum_u16(kcmc_ctx* ctx, const uint16_t* frames_dev, int n_frames, unsigned long long n_px,
+                       const uint8_t* sel_dev, long long* out_sum_dev, kcmc_stream_t stream);
+
+/* out_dev [n_frames, 5] i64 = (sum a, sum b, sum a^2, sum b^2, sum a*b) over the pixels of
+ * rows [y0, y1) and columns [x0, x1), a = frame f of frames_dev [n_frames, H, W] u16 and
+ * b = ref_dev [H, W] u16: the integer moments of Pearson's correlation of every frame with
+ * a reference image.  H * W < 2^31 (sum a*b <= 65535^2 * H * W fits 63 bits); an empty
+ * rectangle is KCMC_EINVAL.  The 16-byte path needs W % 8 == 0 and 16-byte aligned
+ * frames_dev / ref_dev. */
+int kcmc_frame_stats_u16(kcmc_ctx* ctx, const uint16_t* frames_dev, int n_frames, int H, int W,
+                         const uint16_t* ref_dev, int y0, int y1, int x0, int x1, long long* out_dev,
+                         kcmc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -32,6 +32,7 @@ import torch
 from . import affines as _aff
 from . import multidevice as _md
 from . import pipeline as _pl
+from . import quality as _q
 from . import stages
 from .affines import AlignmentError
 
@@ -129,6 +130,16 @@ class VideoAligner:
     # reference's cv2.BFMatcher() default, VA:194) or "hamming" (NORM_HAMMING, for binary
     # ORB/BRIEF/AKAZE descriptors; csrc/match_hamming.hip).
     MATCH_NORM = "l2"
+    # New (opt-in, kcmc_amd.quality): after the alignment, the mean image of the registered
+    # sample frames, the region valid in every frame and every frame's correlation with the
+    # mean image over it (frame_correlations, mean_image, valid_region, correlation_history).
+    QUALITY_METRICS = False
+    # New (opt-in; > 0 implies the metrics): that many more passes of the hot path, each
+    # against the mean of the best-registered TEMPLATE_REFINE_TOP_FRAC of the previous pass's
+    # sample frames (template_image) instead of one raw frame.  The frames' normalisation,
+    # detection and keypoints are reused; only the template is detected again.
+    TEMPLATE_REFINE_ITERS = 0
+    TEMPLATE_REFINE_TOP_FRAC = 0.5
 
     def __init__(self, logger: LoggerAdapter = None):
         self.logger = logger
@@ -139,6 +150,7 @@ class VideoAligner:
         self.interpolated_idxs = None
         self._kp_template = None
         self._des_template = None
+        self._reset_quality()
 
     # ------------------------------------------------------------------ helpers
     @classmethod
@@ -174,6 +186,90 @@ class VideoAligner:
             frame_downsample_rate=int(frame_downsample_rate), ransac_model=cls.RANSAC_MODEL,
             match_norm=cls.MATCH_NORM)
 
+    # ------------------------------------------------- quality metrics, template refinement
+    def _reset_quality(self) -> None:
+        self.frame_correlations = None
+        self.mean_image = None
+        self.valid_region = None
+        self.template_image = None
+        self.correlation_history = None
+
+    def _quality_on(self, refine_supported: bool = True) -> bool:
+        """Whether the metrics run, after the checks that must fail before any work."""
+        iters = int(self.TEMPLATE_REFINE_ITERS)
+        if iters < 0:
+            raise ValueError("TEMPLATE_REFINE_ITERS must be >= 0")
+        on = bool(self.QUALITY_METRICS) or iters > 0
+        if on and self.RANSAC_MODEL == "projective":
+            raise NotImplementedError("QUALITY_METRICS / TEMPLATE_REFINE_ITERS do not support RANSAC_MODEL = "
+                                      "'projective' (a homography's displacement is not bounded by its corners)")
+        if iters > 0 and not refine_supported:
+            raise ValueError("TEMPLATE_REFINE_ITERS needs a detector for the refined template: use align_images "
+                             "(align_keypoints supports QUALITY_METRICS only)")
+        return on
+
+    def _measure(self, res, n_images: int, rate: int) -> List[int]:
+        """The metrics of one pass (res: a SlabResult or SplitResult, frames still on their
+        devices and unpatched); returns sel0, the sample frames that got a model of their own."""
+        parts = res.aligned if isinstance(res.aligned, (list, tuple)) else [res.aligned]
+        if parts[0].dim() != 3:
+            raise NotImplementedError("QUALITY_METRICS / TEMPLATE_REFINE_ITERS support grayscale stacks [F, H, W] only")
+        H, W = parts[0].shape[1:]
+        skipped = set(int(i) for i in res.skipped)
+        sel0 = [i for i in range(0, n_images, rate) if i not in skipped]
+        sel = np.zeros(n_images, bool)
+        sel[sel0] = True
+        mean0 = _q.mean_image(parts, sel)
+        self.affines = res.affines
+        region = _q.valid_region(np.asarray(res.affines)[:n_images], H, W)
+        corr = _q.frame_correlations(parts, mean0, region)
+        self.mean_image = mean0.cpu().numpy()
+        self.valid_region = region
+        self.frame_correlations = corr
+        self.correlation_history.append(corr)
+        if np.isnan(corr).all():
+            self.logger.info(f"pass {len(self.correlation_history)}: no frame has a defined correlation")
+        else:
+            self.logger.info(f"pass {len(self.correlation_history)}: mean frame correlation with the mean image "
+                             f"{np.nanmean(corr):.6f} over rows [{region[0]}, {region[1]}), columns "
+                             f"[{region[2]}, {region[3]})")
+        return sel0
+
+    def _run_passes(self, hot: Callable, slabs: Sequence[_pl.SlabInputs], n_images: int, rate: int,
+                    detect_template: Optional[Callable] = None):
+        """The hot path (``hot()`` -> SlabResult / SplitResult over ``slabs``) once, and with
+        the switches on the metrics after it and TEMPLATE_REFINE_ITERS more passes, each with
+        the template keypoints ``detect_template(template_u16)`` -> (kp [n, 2], des [n, D])
+        finds in the mean of the previous pass's best-registered sample frames."""
+        res = hot()
+        if not self._quality_on(detect_template is not None):
+            return res
+        iters = int(self.TEMPLATE_REFINE_ITERS)
+        self.correlation_history = []
+        for k in range(iters + 1):
+            try:
+                sel0 = self._measure(res, n_images, rate)
+            except ValueError as e:
+                if iters > 0:
+                    raise AlignmentError(f"template refinement, pass {k + 1}: {e}") from e
+                raise
+            if k == iters:
+                break
+            parts = res.aligned if isinstance(res.aligned, (list, tuple)) else [res.aligned]
+            best = np.zeros(n_images, bool)
+            best[_q.select_top(self.frame_correlations, sel0, float(self.TEMPLATE_REFINE_TOP_FRAC))] = True
+            self.template_image = _q.mean_image(parts, best).cpu().numpy()
+            kp, des = detect_template(self.template_image)
+            self._kp_template = np.asarray(kp, np.float64).reshape(-1, 2)
+            self._des_template = np.asarray(des, np.uint8)
+            for inp in slabs:  # only the template changes between passes
+                dev = inp.frames.device
+                inp.kp_tpl = torch.from_numpy(np.ascontiguousarray(self._kp_template)).to(dev)
+                inp.des_tpl = torch.from_numpy(np.ascontiguousarray(self._des_template)).to(dev)
+            self.logger.info(f"template refined from {int(best.sum())} frames: {len(self._kp_template)} keypoints")
+            res = hot()
+        return res
+
     # ------------------------------------------------------------- public API
     def align_images(
         self,
@@ -190,6 +286,8 @@ class VideoAligner:
         skipped_idxs); with RANSAC_MODEL = "similarity" the transforms are [n, 4] = (tx, ty,
         rotation, scale).  A device tensor input yields a device tensor output.
         """
+        self._reset_quality()
+        self._quality_on()
         self.logger.info(f"aligning {len(images)} frames with n_kp_global: {n_kp_global} and {detector_algorithm}")
         if not 0 <= self.TEMPLATE_FRAME_LOC <= 1:
             raise ValueError("`template_frame_loc` must be between 0 and 1")
@@ -242,8 +340,19 @@ class VideoAligner:
             inp = _pl.SlabInputs(frames, kt.des[0, :n_t].contiguous(), kt.kp[0, :n_t].contiguous(), des_q, kp_q,
                                  q_off, q_off_host)
             self.logger.info(f"identified keypoints in: {round(time.time() - t_start)} s")
-            aligned, eu, skipped = self._align_inputs(inp, n_kp_global, frame_downsample_rate, patch)
+
+            def detect_template(tpl_u16):  # as a masked_template enters: max-scale, downsample, detect
+                t8 = np.ascontiguousarray(self._max_scale_images(None, tpl_u16, brightest_px, np.uint8)[1])
+                t8 = torch.from_numpy(t8).to(dev)[None]
+                k = stages.detect_orb(_pl.downsample_u8(t8, t8, frame_downsample_rate, self.SPATIAL_DOWNSAMPLE_RATE)[1],
+                                      detector.params)
+                n = int(k.count.cpu()[0])
+                return k.kp[0, :n].cpu().numpy(), k.des[0, :n].cpu().numpy()
+
+            aligned, eu, skipped = self._align_inputs(inp, n_kp_global, frame_downsample_rate, patch,
+                                                      detect_template=detect_template)
             return (aligned if on_device else aligned.cpu().numpy()), eu, skipped
+        detect_template = self._host_template_detector(detector, brightest_px, frame_downsample_rate)
         kp_t, des_t = detector.detectAndCompute(template, None)
         self._kp_template = np.array([p.pt for p in kp_t])
         self._des_template = des_t
@@ -254,10 +363,22 @@ class VideoAligner:
             des_list.append(np.asarray(dq, dtype=np.uint8).reshape(len(kq), -1))
         self.logger.info(f"identified keypoints in: {round(time.time() - t_start)} s")
         aligned, eu, skipped = self._align_detected(frames, self._kp_template, self._des_template, kp_list, des_list,
-                                                    n_kp_global, frame_downsample_rate, patch)
+                                                    n_kp_global, frame_downsample_rate, patch,
+                                                    detect_template=detect_template)
         if not on_device:
             aligned = aligned.cpu().numpy()
         return aligned, eu, skipped
+
+    def _host_template_detector(self, detector, brightest_px, rate) -> Callable:
+        """template_u16 -> (kp, des) with a host (OpenCV-style) detector, the way a
+        masked_template enters align_images: max-scale, downsample, detectAndCompute."""
+        def detect_template(tpl_u16):
+            t8 = self._max_scale_images(None, tpl_u16, brightest_px, np.uint8)[1]
+            t8 = self._downsample(t8[None], t8, rate, self.SPATIAL_DOWNSAMPLE_RATE)[1]
+            kp_t, des_t = detector.detectAndCompute(t8, None)
+            return np.array([p.pt for p in kp_t]), des_t
+
+        return detect_template
 
     def _align_images_split(self, images, template, n_kp_global, detector_algorithm, rate, patch, devices, ranges):
         """align_images with the stack split over several devices (kcmc_amd.multidevice):
@@ -301,7 +422,17 @@ class VideoAligner:
                 dev = fr.device
                 slabs.append(_pl.SlabInputs(fr, torch.from_numpy(self._des_template).to(dev),
                                             torch.from_numpy(self._kp_template).to(dev), des_q, kp_q, q_off, q_off_host))
+
+            def detect_template(tpl_u16):  # on the first slab's device, as the first template was
+                t8 = np.ascontiguousarray(self._max_scale_images(None, tpl_u16, brightest_px, np.uint8)[1])
+                with _md._on(u8_parts[0]):
+                    t8 = torch.from_numpy(t8).to(u8_parts[0].device)[None]
+                    k = stages.detect_orb(_pl.downsample_u8(t8, t8, rate, self.SPATIAL_DOWNSAMPLE_RATE)[1],
+                                          detector.params)
+                n = int(k.count.cpu()[0])
+                return k.kp[0, :n].cpu().numpy(), k.des[0, :n].cpu().numpy()
         else:
+            detect_template = self._host_template_detector(detector, brightest_px, rate)
             images_i8 = np.concatenate([u.cpu().numpy() for u in u8_parts])
             images_sample, template = self._downsample(images_i8, template_i8, rate, self.SPATIAL_DOWNSAMPLE_RATE)
             kp_t, des_t = detector.detectAndCompute(template, None)
@@ -316,12 +447,14 @@ class VideoAligner:
             slabs = _md.make_slabs(parts, ranges, np.asarray(des_t, np.uint8), self._kp_template, kp_flat, des_flat,
                                    q_off)
         self.logger.info(f"identified keypoints in: {round(time.time() - t_start)} s")
-        return self._finish_split(slabs, ranges, cfg, patch, images.device if on_device else None)
+        return self._finish_split(slabs, ranges, cfg, patch, images.device if on_device else None, detect_template)
 
-    def _finish_split(self, slabs, ranges, cfg, patch, out_device):
+    def _finish_split(self, slabs, ranges, cfg, patch, out_device, detect_template=None):
         self.logger.info("generating keypoint consensus...")
         t_start = time.time()
-        res = _md.align_split(slabs, ranges, cfg, logger=self.logger)
+        # the metrics read the aligned slabs where they are, before they are gathered
+        res = self._run_passes(lambda: _md.align_split(slabs, ranges, cfg, logger=self.logger), slabs, ranges[-1].f1,
+                               int(cfg.frame_downsample_rate), detect_template)
         self.interpolated_idxs = res.interpolated
         self.logger.info(f"aligned frames in: {round(time.time() - t_start)} s")
         aligned = _md.gather_aligned(res, out_device)
@@ -352,13 +485,16 @@ class VideoAligner:
         """The hot path with precomputed keypoints: per SAMPLE frame
         (images[::max(1, frame_rate // FRAME_SAMPLE_RATE)]) keypoint coordinates [n, 2]
         and uint8 descriptors [n, D]; template keypoints/descriptors likewise."""
+        self._reset_quality()
+        self._quality_on(refine_supported=False)
         self._kp_template = np.asarray(kp_template, dtype=np.float64).reshape(-1, 2)
         self._des_template = np.asarray(des_template, dtype=np.uint8)
         rate = max(1, frame_rate // self.FRAME_SAMPLE_RATE)
         return self._align_detected(images, self._kp_template, self._des_template, list(kp_query), list(des_query),
                                     n_kp_global, rate, patch)
 
-    def _align_detected(self, images, kp_template, des_template, kp_list, des_list, n_kp_global, rate, patch):
+    def _align_detected(self, images, kp_template, des_template, kp_list, des_list, n_kp_global, rate, patch,
+                        detect_template=None):
         to_host = not isinstance(images, torch.Tensor)
         kp_flat, des_flat, q_off = self._csr(kp_list, des_list, des_template.shape[1])
         devices = self._devices()
@@ -367,7 +503,7 @@ class VideoAligner:
             parts = _md.split_to_devices(images if not to_host else np.asarray(images), ranges, devices)
             slabs = _md.make_slabs(parts, ranges, des_template, kp_template, kp_flat, des_flat, q_off)
             return self._finish_split(slabs, ranges, self._config(n_kp_global, rate), patch,
-                                      None if to_host else images.device)
+                                      None if to_host else images.device, detect_template)
         dev = torch.device("cuda", devices[0])
         frames = torch.from_numpy(np.ascontiguousarray(images)).to(dev) if to_host else images.contiguous()
         inp = _pl.SlabInputs(
@@ -379,13 +515,14 @@ class VideoAligner:
             q_off=torch.from_numpy(q_off).to(dev),
             q_off_host=q_off,
         )
-        return self._align_inputs(inp, n_kp_global, rate, patch, to_host=to_host)
+        return self._align_inputs(inp, n_kp_global, rate, patch, to_host=to_host, detect_template=detect_template)
 
-    def _align_inputs(self, inp, n_kp_global, rate, patch, to_host: bool = False):
+    def _align_inputs(self, inp, n_kp_global, rate, patch, to_host: bool = False, detect_template=None):
         cfg = self._config(n_kp_global, rate)
         self.logger.info("generating keypoint consensus...")
         t_start = time.time()
-        res = _pl.align_slab(inp, cfg, logger=self.logger)
+        res = self._run_passes(lambda: _pl.align_slab(inp, cfg, logger=self.logger), [inp], inp.frames.shape[0], rate,
+                               detect_template)
         self.interpolated_idxs = res.interpolated
         self.logger.info(f"aligned frames in: {round(time.time() - t_start)} s")
         aligned = res.aligned
