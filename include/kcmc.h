@@ -261,7 +261,10 @@ int kcmc_ransac_rigid(kcmc_ctx* ctx, const double* src_dev, const double* dst_de
  *   out_params_dev   [n_frames, 2, 3] f64  model.params[:2] = [scale * R | t],
  *                                          translation * spatial_rate
  * Its parity with skimage rests on an operation-for-operation numpy restatement
- * (tests/test_similarity_host.py), not on a golden from skimage itself. */
+ * (tests/test_similarity_host.py), not on a golden from skimage itself.  The bit-exact
+ * yardstick of the selection (winning trial, inlier count and mask) is the C oracle
+ * kcmc_oracle_ransac_similarity (oracle/kcmc_oracle.c, test infrastructure), the same
+ * closed form, itself pinned to that restatement. */
 int kcmc_ransac_similarity(kcmc_ctx* ctx, const double* src_dev, const double* dst_dev,
                            const int32_t* pt_idx_dev, const int32_t* pt_off_dev, int src_frame_stride,
                            int n_frames, int max_n, int trials, double residual_threshold,

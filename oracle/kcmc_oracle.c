@@ -12,6 +12,9 @@
  *   - kcmc_oracle_ransac_rigid: pinned against the reference's own
  *     _compute_euclidean_affine (VA:288-323, scikit-image 0.18.3 ransac) run in
  *     the authoring container -> tests/golden/ransac_golden.npz.
+ *   - kcmc_oracle_ransac_similarity: scikit-image is absent from this image, so no
+ *     golden exists; pinned against the operation-for-operation numpy restatement of
+ *     ransac + SimilarityTransform (SVD Umeyama) in tests/test_similarity_host.py.
  *   - kcmc_oracle_knn2_l2u8 and kcmc_oracle_warp_affine_u16: OpenCV is absent
  *     everywhere in this image, so these restate OpenCV 4.x's classic algorithms
  *     (core/src/batch_distance.cpp batchDistL2_8u32f + K-insertion;
@@ -433,13 +436,61 @@ static int rigid_fit(const double* src, const double* dst, const int* sel, int n
   return 0;
 }
 
-/* src = frame keypoints, dst = template keypoints (VA:310).  hyp = [T,2] sample
- * indices (trial t uses hyp[t]; numpy RandomState(seed).choice(N, 2, False)).
- * out_params [2,3] (NaN when no model), out_inliers [N] (0/1).
- * Returns 0 when a model was fitted, 1 when skimage would return None. */
-int kcmc_oracle_ransac_rigid(const double* src, const double* dst, int N, const int32_t* hyp,
-                             int T, double thresh, double* out_params, uint8_t* out_inliers,
-                             int32_t* out_best_trial, int32_t* out_n_inliers) {
+/* Similarity least-squares fit (skimage _umeyama with estimate_scale=True) in closed
+ * form.  With a = a00 + a11, b = a10 - a01 as in rigid_fit, a^2 + b^2 = (s1 +- s2)^2 of
+ * A's singular values (the sign of det A), so skimage's scale * R has the entries
+ * a / v and b / v with v = sum |src_d|^2 and no root is taken.  v is summed per column
+ * in point order and the two column sums are added last: numpy's
+ * src_demean.var(axis=0).sum(), and for two points the kernel's
+ * (a0 a0 + b0 b0) + (a1 a1 + b1 b1); a per-point sum rounds differently and breaks the
+ * bit-exact selection.  Returns 1 (no model) when a == 0 && b == 0, which covers v == 0.
+ * Not restated: a pure reflection with a == b == 0 exactly, where skimage's rank-2 branch
+ * returns a scale-0 map and this form returns no model. */
+static int similarity_fit(const double* src, const double* dst, const int* sel, int n, double* P) {
+  double ms0 = 0, ms1 = 0, md0 = 0, md1 = 0;
+  for (int k = 0; k < n; ++k) {
+    int q = sel ? sel[k] : k;
+    ms0 += src[2 * q];
+    ms1 += src[2 * q + 1];
+    md0 += dst[2 * q];
+    md1 += dst[2 * q + 1];
+  }
+  ms0 /= n;
+  ms1 /= n;
+  md0 /= n;
+  md1 /= n;
+  double a00 = 0, a01 = 0, a10 = 0, a11 = 0, v0 = 0, v1 = 0;
+  for (int k = 0; k < n; ++k) {
+    int q = sel ? sel[k] : k;
+    double s0 = src[2 * q] - ms0, s1 = src[2 * q + 1] - ms1;
+    double d0 = dst[2 * q] - md0, d1 = dst[2 * q + 1] - md1;
+    a00 += d0 * s0;
+    a01 += d0 * s1;
+    a10 += d1 * s0;
+    a11 += d1 * s1;
+    v0 += s0 * s0;
+    v1 += s1 * s1;
+  }
+  double a = a00 + a11, b = a10 - a01;
+  if (a == 0 && b == 0) return 1;
+  double v = v0 + v1;
+  double c = a / v, s = b / v;
+  P[0] = c;
+  P[1] = -s;
+  P[3] = s;
+  P[4] = c;
+  P[2] = md0 - (c * ms0 - s * ms1);
+  P[5] = md1 - (s * ms0 + c * ms1);
+  return 0;
+}
+
+typedef int (*fit_fn)(const double*, const double*, const int*, int, double*);
+
+/* The loop of skimage ransac(min_samples=2) around a two-point model's fit: shared by the
+ * rigid and the similarity oracle, which differ in the fit alone. */
+static int ransac_two_point(fit_fn fit, const double* src, const double* dst, int N, const int32_t* hyp,
+                            int T, double thresh, double* out_params, uint8_t* out_inliers,
+                            int32_t* out_best_trial, int32_t* out_n_inliers) {
   double* r2 = (double*)malloc(sizeof(double) * (size_t)(N > 0 ? N : 1));
   uint8_t* cur = (uint8_t*)malloc((size_t)(N > 0 ? N : 1));
   int* sel = (int*)malloc(sizeof(int) * (size_t)(N > 0 ? N : 1));
@@ -455,7 +506,7 @@ int kcmc_oracle_ransac_rigid(const double* src, const double* dst, int N, const 
   for (int t = 0; t < T; ++t) {
     int pair[2] = {hyp[2 * t], hyp[2 * t + 1]};
     double P[6];
-    if (rigid_fit(src, dst, pair, 2, P)) continue; /* NaN model: count 0, S NaN */
+    if (fit(src, dst, pair, 2, P)) continue; /* NaN model: count 0, S NaN */
     int cnt = 0;
     for (int k = 0; k < N; ++k) {
       double x = src[2 * k], y = src[2 * k + 1];
@@ -481,7 +532,7 @@ int kcmc_oracle_ransac_rigid(const double* src, const double* dst, int N, const 
     int m = 0;
     for (int k = 0; k < N; ++k)
       if (out_inliers[k]) sel[m++] = k;
-    rc = rigid_fit(src, dst, sel, m, out_params);
+    rc = fit(src, dst, sel, m, out_params);
   }
   if (rc) {
     for (int k = 0; k < 6; ++k) out_params[k] = NAN;
@@ -493,6 +544,27 @@ int kcmc_oracle_ransac_rigid(const double* src, const double* dst, int N, const 
   free(cur);
   free(sel);
   return rc;
+}
+
+/* src = frame keypoints, dst = template keypoints (VA:310).  hyp = [T,2] sample
+ * indices (trial t uses hyp[t]; numpy RandomState(seed).choice(N, 2, False)).
+ * out_params [2,3] (NaN when no model), out_inliers [N] (0/1).
+ * Returns 0 when a model was fitted, 1 when skimage would return None. */
+int kcmc_oracle_ransac_rigid(const double* src, const double* dst, int N, const int32_t* hyp,
+                             int T, double thresh, double* out_params, uint8_t* out_inliers,
+                             int32_t* out_best_trial, int32_t* out_n_inliers) {
+  return ransac_two_point(rigid_fit, src, dst, N, hyp, T, thresh, out_params, out_inliers, out_best_trial,
+                          out_n_inliers);
+}
+
+/* K2s oracle: skimage 0.18.3 ransac(SimilarityTransform, min_samples=2, ...), the build's
+ * similarity model (an extension: the reference only uses EuclideanTransform, VA:311).
+ * Same arguments, return codes and loop as kcmc_oracle_ransac_rigid. */
+int kcmc_oracle_ransac_similarity(const double* src, const double* dst, int N, const int32_t* hyp,
+                                  int T, double thresh, double* out_params, uint8_t* out_inliers,
+                                  int32_t* out_best_trial, int32_t* out_n_inliers) {
+  return ransac_two_point(similarity_fit, src, dst, N, hyp, T, thresh, out_params, out_inliers, out_best_trial,
+                          out_n_inliers);
 }
 
 /* ------------------------------------------------------------------------- */

@@ -10,7 +10,9 @@ Contents
 --------
 * ctypes wrappers over ``libkcmc_oracle.so`` (``kcmc_oracle.c``): OpenCV knnMatch
   (NORM_L2, k=2), OpenCV classic warpAffine INTER_LINEAR on uint16, closed-form
-  rigid RANSAC with skimage 0.18.3 selection semantics.
+  rigid RANSAC with skimage 0.18.3 selection semantics, and the same loop around the
+  scaled Umeyama fit (``ransac_similarity``: skimage's SimilarityTransform, the build's
+  similarity model).
 * ``hypothesis_table``: the seeded sample stream skimage consumes
   (``np.random.RandomState(42).choice(N, 2, replace=False)`` per trial, skimage
   fit.py:819-826), generated with numpy itself.
@@ -23,7 +25,9 @@ Contents
 * ``consensus`` / ``lookup``: VA:224-286 with real CPython ``set``/``Counter``.
 
 Pinning: the RANSAC/consensus/filter restatements are checked against fixtures
-made by running the reference's own code (tests/golden/make_golden.py); knnMatch
+made by running the reference's own code (tests/golden/make_golden.py); the
+similarity RANSAC has no such fixture (scikit-image is absent here) and is pinned to
+the numpy SVD restatement in tests/test_similarity_host.py; knnMatch
 and warpAffine are pinned only by hand-computed known-answer tests because
 OpenCV is absent from this image ("parity vs real OpenCV unpinned").
 """
@@ -46,7 +50,9 @@ def lib() -> ctypes.CDLL:
     global _LIB
     if _LIB is None:
         path = os.path.join(_HERE, "libkcmc_oracle.so")
-        if not os.path.exists(path):
+        src = os.path.join(_HERE, "kcmc_oracle.c")
+        # a library older than its source lacks the newer entries: rebuild it too
+        if not os.path.exists(path) or (os.path.exists(src) and os.path.getmtime(src) > os.path.getmtime(path)):
             import subprocess
 
             subprocess.check_call(["make", "-s", "-C", _HERE])
@@ -60,6 +66,7 @@ def lib() -> ctypes.CDLL:
         L.kcmc_oracle_pairwise_sum.argtypes = [P, i]
         L.kcmc_oracle_pairwise_sum.restype = ctypes.c_double
         L.kcmc_oracle_ransac_rigid.argtypes = [P, P, i, P, i, ctypes.c_double, P, P, P, P]
+        L.kcmc_oracle_ransac_similarity.argtypes = [P, P, i, P, i, ctypes.c_double, P, P, P, P]
         L.kcmc_oracle_knn2_l2f32.argtypes = [P, i, P, i, i, P, P]
         L.kcmc_oracle_orb_detect.argtypes = [P, i, i, i, i, ctypes.c_double, i, P, P, P, P]
         L.kcmc_oracle_fast_score.argtypes = [P, i, i, i]
@@ -192,6 +199,20 @@ def ransac_rigid(src: np.ndarray, dst: np.ndarray, trials: int = 1000, thresh: f
     src = frame keypoints, dst = template keypoints.  Returns
     (params [2,3] (NaN if no model), inliers bool [N], best_trial, n_inliers).
     """
+    return _ransac_two_point(lib().kcmc_oracle_ransac_rigid, src, dst, trials, thresh, seed)
+
+
+def ransac_similarity(src: np.ndarray, dst: np.ndarray, trials: int = 1000, thresh: float = 2.0, seed: int = 42):
+    """Closed-form restatement of skimage ransac + SimilarityTransform (min_samples=2): the
+    loop of ``ransac_rigid`` around the scaled Umeyama fit (kcmc_oracle_ransac_similarity).
+
+    src = frame keypoints, dst = template keypoints.  Returns
+    (params [2,3] (NaN if no model), inliers bool [N], best_trial, n_inliers).
+    """
+    return _ransac_two_point(lib().kcmc_oracle_ransac_similarity, src, dst, trials, thresh, seed)
+
+
+def _ransac_two_point(entry, src, dst, trials, thresh, seed):
     src = np.ascontiguousarray(src, np.float64)
     dst = np.ascontiguousarray(dst, np.float64)
     n = src.shape[0]
@@ -200,7 +221,7 @@ def ransac_rigid(src: np.ndarray, dst: np.ndarray, trials: int = 1000, thresh: f
     inl = np.zeros(max(n, 1), np.uint8)
     bt = np.zeros(1, np.int32)
     ni = np.zeros(1, np.int32)
-    lib().kcmc_oracle_ransac_rigid(_p(src), _p(dst), n, _p(hyp), trials, float(thresh), _p(params), _p(inl), _p(bt), _p(ni))
+    entry(_p(src), _p(dst), n, _p(hyp), trials, float(thresh), _p(params), _p(inl), _p(bt), _p(ni))
     return params, inl[:n].astype(bool), int(bt[0]), int(ni[0])
 
 

@@ -65,6 +65,8 @@ def _oracle_stages(model="euclidean", no_model=False):
             if len(L) >= cfg.effective_frame_skip and not no_model:
                 if model == "euclidean":
                     out[f] = oracle.ransac_rigid(kq[f][L], kt[L])[0]
+                elif model == "similarity":
+                    out[f] = oracle.ransac_similarity(kq[f][L], kt[L])[0]
                 else:
                     out[f] = oracle.ransac_model(kq[f][L], kt[L], model)[0][: out.shape[1]]
         return torch.from_numpy(out)
@@ -122,7 +124,7 @@ def _free_port():
 @pytest.mark.timeout(300)
 @pytest.mark.parametrize("model,world,nan_rank", [("euclidean", 2, None), ("affine", 2, None), ("projective", 2, None),
                                                   ("euclidean", 3, 1), ("euclidean", 3, 0), ("euclidean", 3, 2),
-                                                  ("affine", 3, 1)])
+                                                  ("affine", 3, 1), ("similarity", 2, None), ("similarity", 3, 1)])
 def test_sharded_pipeline_matches_single_process(tmp_path, model, world, nan_rank):
     mp.spawn(_worker, args=(world, _free_port(), str(tmp_path), model, nan_rank), nprocs=world, join=True)
     r = [np.load(os.path.join(tmp_path, f"rank{k}.npz")) for k in range(world)]

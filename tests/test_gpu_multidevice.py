@@ -40,7 +40,8 @@ def _keypoint_stack(n_sample, rate, model, blind, seed=61):
 
 
 @pytest.mark.parametrize("model,rate,blind", [("euclidean", 1, (5, 6, 7)), ("euclidean", 2, (4, 5)),
-                                              ("affine", 1, (0, 1, 6)), ("euclidean", 1, (10, 11))])
+                                              ("affine", 1, (0, 1, 6)), ("euclidean", 1, (10, 11)),
+                                              ("similarity", 1, (5, 6, 7))])
 def test_two_slabs_on_one_gpu_equal_one_slab(dev, model, rate, blind):
     n_sample = 12
     ks, frames, kq, dq = _keypoint_stack(n_sample, rate, model, blind)

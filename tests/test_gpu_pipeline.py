@@ -242,7 +242,8 @@ def test_euclidean_min_samples_other_than_two_raises(dev):
 
 
 @pytest.mark.parametrize("model,rate,beside", [("euclidean", 2, True), ("euclidean", 3, False),
-                                               ("projective", 1, False), ("projective", 1, True)])
+                                               ("projective", 1, False), ("projective", 1, True),
+                                               ("similarity", 1, True)])
 def test_overlapped_slabs_host_maps_and_projective(dev, model, rate, beside):
     """The OverlappedSlabs paths test_overlapped_slabs_equal_align_slab does not reach:
     frame_downsample_rate > 1 (every full-rate frame's map comes from the host NaN-padding

@@ -110,7 +110,8 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.timeout(240)
 @pytest.mark.parametrize("model,world,blind,beside", [("euclidean", 2, False, False), ("affine", 2, False, True),
-                                                     ("euclidean", 3, True, False), ("affine", 3, True, True)])
+                                                     ("euclidean", 3, True, False), ("affine", 3, True, True),
+                                                     ("similarity", 2, False, False), ("similarity", 3, True, True)])
 def test_sharded_hip_path_equals_single_device(tmp_path, model, world, blind, beside):
     """beside: the pipelined schedule with the match on the analysis stream (c2-c4's)."""
     port = _free_port()

@@ -3,7 +3,13 @@ estimated) against the numpy restatement of scikit-image 0.18.3's
 ransac(..., SimilarityTransform, min_samples=2, ...) in tests/test_similarity_host.py, and
 the model through the pipeline and the VideoAligner API.  Inlier sets and the winning sample
 pair exact, parameters within the closed-form-vs-SVD bound (rtol 1e-8, atol 1e-9), warped
-pixels bit-exact to the oracle."""
+pixels bit-exact to the oracle.
+
+And against the C oracle (oracle.ransac_similarity, the same closed form, pinned to the
+restatement on the host): winning trial index, inlier count and mask bit for bit on a fuzz
+over sizes, coordinate scales, rotations and scales 0.25 to 4, on points within 1e-12 of
+the threshold under scales 0.4 and 2.5, on every path size up to N = 2000 and on degenerate
+frames; parameters at rtol 1e-10, atol 1e-10 max(1, |template|max)."""
 import numpy as np
 import pytest
 import torch
@@ -156,6 +162,116 @@ def test_thresholds_exact_only_path_and_undecided_band(dev, thresh):
     tpls, qs = host.threshold_frames()
     off, params, inl, nin, best = _run(dev, tpls, qs, residual_threshold=thresh)
     _check_vs_reference(f"thresh{thresh:g}", off, params, inl, nin, best, 1000)
+
+
+# ------------------------------------------------------------- the kernel against the C oracle
+# oracle.ransac_similarity is the closed form the kernel computes (pinned to the restatement
+# in tests/test_similarity_host.py), so the comparison is bit for bit on selection: winning
+# trial index, inlier count and mask.  Only the refit's summation order differs: parameters
+# at the rigid fuzz's tolerance.
+def _check_vs_oracle(tpls, qs, got, thresh=2.0, trials=1000, ctx=()):
+    off, params, inl, nin, best = got
+    worst, n_fit = 0.0, 0
+    for f, (tpl, q) in enumerate(zip(tpls, qs)):
+        m = inl[off[f]:off[f + 1]]
+        if len(q) < 3:  # below N_KP_FRAME_SKIP: NaN, no inliers, no trial
+            assert np.isnan(params[f]).all() and nin[f] == 0 and best[f] == -1 and not m.any(), (ctx, f)
+            continue
+        p, i_ref, bt, ni = oracle.ransac_similarity(q, tpl, trials, thresh)
+        assert best[f] == bt and nin[f] == ni, (ctx, f, len(q), best[f], bt, nin[f], ni)
+        assert np.array_equal(m, i_ref), (ctx, f)
+        sc = max(1.0, float(np.abs(tpl).max()))
+        np.testing.assert_allclose(params[f], p, rtol=1e-10, atol=1e-10 * sc, equal_nan=True, err_msg=str((ctx, f)))
+        if not np.isnan(p).any():
+            worst = max(worst, float(np.abs(params[f] - p).max()) / sc)
+            n_fit += 1
+    print(f"{ctx}: {len(qs)} frames, {n_fit} fitted, kernel vs oracle max |dp| / scale {worst:.3g}")
+    return n_fit
+
+
+def _fuzz_set(s):
+    """host.fuzz_set widened for two closed forms: N = 0, 1, 2 (skipped frames) and noise-free
+    frames (S rounds to 0 in some trials: the early exit must agree)."""
+    return host.fuzz_set(s, extra_n=(0, 1, 2), extra_noise=(0.0,))
+
+
+@pytest.mark.parametrize("s", host.FUZZ_SEEDS)
+def test_fuzz_vs_oracle(dev, s):
+    tpls, qs, thresh = _fuzz_set(s)
+    assert len(qs) == 24
+    n_fit = _check_vs_oracle(tpls, qs, _run(dev, tpls, qs, residual_threshold=thresh), thresh, ctx=("fuzz", s, thresh))
+    assert n_fit >= 8  # 3 of the 8 choices of N are skipped frames: a third of the 24 at least is fitted
+
+
+@pytest.mark.parametrize("k", [0.4, 2.5])
+@pytest.mark.parametrize("scale", [1.0, 2000.0, 3e5])
+def test_threshold_band_vs_oracle(dev, scale, k):
+    """test_gpu_fuzz.test_ransac_threshold_band_vs_oracle's frames under a similarity of scale
+    k (|a|, |b| of the fp32 phase A's bound |a| h_x + |b| h_y above and far below 1), with
+    2.0 rad more rotation on odd frames: points within 1e-12 .. 1e-2 of the 2 px threshold,
+    coordinates up to 3e5 px (wide band, trials deferred to the fp64 phase A).  The band lies
+    inside the SVD's rounding, so only the closed-form oracle can be the yardstick here."""
+    rng = np.random.default_rng(int(scale) + int(10 * k))
+    tpls, qs = [], []
+    for f in range(6):
+        n_exact, n_band, n_out = 12 + 3 * f, 20, 10
+        tpl = rng.uniform(0.2, 1.0, (n_exact + n_band + n_out, 2)) * scale
+        a = rng.normal(0, 0.02) + (2.0 if f % 2 else 0.0)
+        A = k * np.array([[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]])
+        t = rng.normal(0, 5, 2)
+        q = (tpl - t) @ np.linalg.inv(A).T  # q maps onto tpl exactly: A q + t = tpl
+        d = rng.choice([-1e-2, -1e-5, -1e-9, -1e-12, 0.0, 1e-12, 1e-9, 1e-5, 1e-2], n_band)
+        ang = rng.uniform(0, 2 * np.pi, n_band)
+        sl = slice(n_exact, n_exact + n_band)
+        tpl[sl] += (2.0 + d)[:, None] * np.stack([np.cos(ang), np.sin(ang)], 1)
+        tpl[n_exact + n_band:] += rng.uniform(5, 50, (n_out, 2))
+        tpls.append(tpl)
+        qs.append(q)
+    assert _check_vs_oracle(tpls, qs, _run(dev, tpls, qs), ctx=("band", scale, k)) == 6
+
+
+PATH_NS = [3, 4, 5, 8, 9, 50, 63, 64, 65, 100, 127, 128, 129, 136, 200, 255, 256, 257, 300, 500, 777, 1024, 2000]
+
+
+def test_path_sizes_winning_trial_vs_oracle(dev):
+    """test_gpu_kernels.test_ransac_bit_exact_selection_vs_oracle's frames with a per-frame
+    scale in [0.5, 2]: every N at which the kernel changes path, up to the 2000 points of the
+    rigid list (numpy's split plan four levels deep), and the winning trial by its index."""
+    rng = np.random.default_rng(21)
+    tpls, qs = [], []
+    for N in PATH_NS:
+        tpl = rng.uniform(0, 1000, (N, 2))
+        A = synthetic.rigid(rng.normal(0, 0.02), rng.normal(0, 5), rng.normal(0, 5))
+        s = rng.uniform(0.5, 2.0)
+        q = (tpl - A[:, 2]) @ A[:, :2] / s + rng.normal(0, rng.uniform(0.1, 1.5), (N, 2))
+        out = rng.random(N) < rng.uniform(0, 0.6)
+        q[out] = rng.uniform(0, 1000, (int(out.sum()), 2))
+        tpls.append(host._f32(tpl))
+        qs.append(host._f32(q))
+    assert _check_vs_oracle(tpls, qs, _run(dev, tpls, qs), ctx="path sizes") == len(PATH_NS)
+
+
+def test_degenerate_frames_vs_oracle(dev):
+    """host.degenerate_frames (coincident thirds on either side, a quarter turn with scale 3, a
+    mirrored frame: refit with det < 0) and a frame whose points all coincide: no trial has a
+    model, so NaN, no inliers, trial -1."""
+    frames = host.degenerate_frames()
+    tpls, qs = [t for _, _, t, _ in frames], [q for _, _, _, q in frames]
+    rng = np.random.default_rng(23)
+    tpls.append(rng.uniform(0, 100, (10, 2)))
+    qs.append(np.repeat(rng.uniform(0, 100, (1, 2)), 10, 0))
+    got = _run(dev, tpls, qs)
+    assert _check_vs_oracle(tpls, qs, got, ctx="degenerate") == 8
+    off, params, inl, nin, best = got
+    assert np.isnan(params[-1]).all() and nin[-1] == 0 and best[-1] == -1 and not inl[off[-2]:].any()
+
+
+@pytest.mark.parametrize("thresh", host.THRESHOLDS)
+def test_fuzz_first_seed_at_extreme_thresholds_vs_oracle(dev, thresh):
+    """1e-120 (exact scoring only: a point is an inlier only at residual 0, and a trial with
+    no inlier can still win on S) and 5e-5 on frames of every coordinate scale."""
+    tpls, qs, _ = _fuzz_set(0)
+    _check_vs_oracle(tpls, qs, _run(dev, tpls, qs, residual_threshold=thresh), thresh, ctx=("fuzz 0", thresh))
 
 
 def _pipeline_inputs(dev):

@@ -65,7 +65,8 @@ def _cpu_slabs(ks, frames, ranges):
 
 
 @pytest.mark.parametrize("model,rate,blind", [("euclidean", 1, (4, 5, 6)), ("euclidean", 2, (0, 1, 5)),
-                                              ("affine", 1, (3, 4, 5, 6, 7)), ("euclidean", 1, (8, 9))])
+                                              ("affine", 1, (3, 4, 5, 6, 7)), ("euclidean", 1, (8, 9)),
+                                              ("similarity", 1, (3, 4, 5, 6))])
 def test_split_equals_one_slab(model, rate, blind):
     n_sample = 10
     ks, frames = _stack(n_sample, rate, model, blind)

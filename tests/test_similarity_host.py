@@ -265,6 +265,82 @@ def input_sets():
 SET_NAMES = ["selection", "selection200", "exact", "rigid", "pipeline"] + [f"thresh{th:g}" for th in THRESHOLDS]
 
 
+FUZZ_SEEDS = range(6)
+FUZZ_FRAMES = 24
+FUZZ_THRESHOLDS = [2.0, 0.5, 5.0, 1e-3]
+
+
+def fuzz_frames(rng, n_frames, extra_n=(), extra_noise=()):
+    """Random (template, frame) point sets: 3 to 400 points, coordinate scales 1e-2 to 1e4,
+    any rotation, scales 0.25 to 4, noise from 1e-9 to 1.5 px (scaled with large coordinates),
+    up to half outliers, mirrored frames (refit with det < 0) and duplicated halves.  No frame
+    is noise-free by default: with S == 0 the SVD and the closed form legitimately stop at
+    different trials.  extra_n / extra_noise widen the choices of N and of the noise for the
+    comparison of two closed forms (tests/test_gpu_similarity.py)."""
+    for _ in range(n_frames):
+        N = int(rng.choice([3, 4, 5, int(rng.integers(6, 60)), int(rng.integers(60, 400))] + list(extra_n)))
+        scale = 10.0 ** rng.uniform(-2, 4)
+        tpl = rng.uniform(0, scale, (N, 2))
+        a = rng.uniform(-np.pi, np.pi) if rng.random() < 0.5 else rng.normal(0, 0.05)
+        k = float(rng.choice([0.25, 0.5, 0.8, 1.0, 1.25, 2.0, 4.0])) * rng.uniform(0.95, 1.05)
+        A = k * np.array([[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]])
+        q = tpl @ A.T + rng.normal(0, scale * 0.01, 2)
+        noise = rng.choice([1e-9, 0.3, 1.5] + list(extra_noise)) * (scale / 1000.0 if scale > 1000 else 1.0)
+        q = q + rng.normal(0, noise, (N, 2))
+        out = rng.random(N) < rng.uniform(0, 0.5)
+        q[out] = rng.uniform(0, scale, (int(out.sum()), 2))
+        if rng.random() < 0.15:
+            q[:, 1] = -q[:, 1]                      # mirrored frame
+        if N > 10 and rng.random() < 0.3:
+            q[N // 2:], tpl[N // 2:] = q[: N - N // 2], tpl[: N - N // 2]
+        yield tpl, q
+
+
+def fuzz_set(s, **widen):
+    """Seed 5000 + s: the threshold (drawn before the frames) and the 24 frames."""
+    rng = np.random.default_rng(5000 + s)
+    thresh = float(rng.choice(FUZZ_THRESHOLDS))
+    tpls, qs = zip(*fuzz_frames(rng, FUZZ_FRAMES, **widen))
+    return list(tpls), list(qs), thresh
+
+
+DEGENERATE_KINDS = ["frame_third_identical", "template_third_identical", "quarter_turn_scale3", "mirrored_x"]
+
+
+def degenerate_frames():
+    """(kind, N, template points, frame points) for N = 30 and 140: both sides share a
+    0.03 rad, scale 1.07 map with 0.4 px noise, then a third of the frame points coincide,
+    a third of the template points coincide, the map is a rotation by pi/2 + 0.01 with
+    scale 3, or the frame's x is mirrored (the refit's covariance has det < 0)."""
+    rng = np.random.default_rng(97)
+    out = []
+    for N in (30, 140):
+        for kind in DEGENERATE_KINDS:
+            a, k = (np.pi / 2 + 0.01, 3.0) if kind == "quarter_turn_scale3" else (0.03, 1.07)
+            A = k * np.array([[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]])
+            q = rng.uniform(0, 300, (N, 2))
+            tpl = q @ A.T + rng.normal(0, 5, 2) + rng.normal(0, 0.4, (N, 2))
+            if kind == "frame_third_identical":
+                q[: N // 3] = q[0]
+            elif kind == "template_third_identical":
+                tpl[: N // 3] = tpl[0]
+            elif kind == "mirrored_x":
+                q[:, 0] = -q[:, 0]
+            out.append((kind, N, tpl, q))
+    return out
+
+
+def large_frame(N=1024):
+    """One frame well above the other sets' 300 points (numpy's split plan three levels deep)."""
+    rng = np.random.default_rng(98)
+    tpl = rng.uniform(0, 1000, (N, 2))
+    A = _sim_map(rng, 0.7, 1.4)
+    q = synthetic.apply_map(np.linalg.inv(np.vstack([A, [0, 0, 1.0]])), tpl) + rng.normal(0, 0.7, (N, 2))
+    out = rng.random(N) < 0.3
+    q[out] = rng.uniform(0, 1000, (int(out.sum()), 2))
+    return tpl, q
+
+
 @functools.lru_cache(maxsize=None)
 def reference(name):
     """The restatement's result for every frame of an input set (computed once per session;
@@ -305,6 +381,88 @@ def test_closed_form_agrees_with_the_restatement(name):
         n_fit += not np.isnan(p_ref).any()
     if not name.startswith("thresh1e-120"):
         assert n_fit >= len(qs) - 3, name  # the sets exercise fits, not only failures
+
+
+# ------------------------------------------------------ the C oracle against the restatement
+def _sample_rows(tpl, q, pair):
+    """A sample as the set of its (frame point, template point) coordinate rows: duplicated
+    rows make different index pairs the same hypothesis."""
+    return None if pair is None else frozenset((*map(float, q[k]), *map(float, tpl[k])) for k in pair)
+
+
+def check_oracle_vs_restatement(tpl, q, trials, thresh, ref=None, compare_pair=True, ctx=None):
+    """oracle.ransac_similarity (C, closed form) against ransac_similarity_skimage on one
+    frame: inlier mask and count exact, the winning sample as coordinate rows, parameters at
+    RTOL with atol = ATOL max(1, |tpl|max).  Returns the largest parameter deviation divided
+    by max(1, |tpl|max) (0 when there is no model)."""
+    p_ref, inl_ref, pair_ref, ni_ref = ref if ref is not None else ransac_similarity_skimage(q, tpl, trials, thresh)
+    p, inl, bt, ni = oracle.ransac_similarity(q, tpl, trials, thresh)
+    assert np.array_equal(inl, inl_ref), ctx
+    assert ni == ni_ref, ctx
+    if compare_pair:
+        pair = None if bt < 0 else [int(k) for k in oracle.hypothesis_table(len(q), trials)[bt]]
+        assert _sample_rows(tpl, q, pair) == _sample_rows(tpl, q, pair_ref), (ctx, bt)
+    sc = max(1.0, float(np.abs(tpl).max()))
+    np.testing.assert_allclose(p, p_ref, rtol=RTOL, atol=ATOL * sc, equal_nan=True, err_msg=str(ctx))
+    return 0.0 if np.isnan(p_ref).any() else float(np.abs(p - p_ref).max()) / sc
+
+
+@pytest.mark.parametrize("name", SET_NAMES)
+def test_oracle_agrees_with_the_restatement_on_the_input_sets(name):
+    """Every frame of every existing input set, under the rule of
+    test_closed_form_agrees_with_the_restatement (no pair comparison on "exact").  A frame of
+    two points, which every caller skips, is compared as well: both loops accept it (the
+    pipeline set's two blanked frames have no point at all, so no sample can be drawn)."""
+    tpls, qs, trials, thresh = input_sets()[name]
+    worst = 0.0
+    assert sum(len(q) < 2 for q in qs) == (len(PIPE["blank"]) if name == "pipeline" else 0)
+    for f, (tpl, q, ref) in enumerate(zip(tpls, qs, reference(name))):
+        if len(q) < 2:
+            continue
+        worst = max(worst,check_oracle_vs_restatement(tpl, q, trials, thresh, ref=ref if len(q) >= 3 else None,
+                                                       compare_pair=name != "exact", ctx=(name, f)))
+    print(f"{name}: {len(qs)} frames, max |dp| / scale {worst:.3g}")
+
+
+@pytest.mark.parametrize("s", FUZZ_SEEDS)
+def test_oracle_agrees_with_the_restatement_on_the_fuzz(s):
+    tpls, qs, thresh = fuzz_set(s)
+    assert len(qs) == FUZZ_FRAMES
+    worst = 0.0
+    for f, (tpl, q) in enumerate(zip(tpls, qs)):
+        worst = max(worst, check_oracle_vs_restatement(tpl, q, 1000, thresh, ctx=(s, f, len(q), thresh)))
+    print(f"fuzz seed {5000 + s} thresh {thresh:g}: max |dp| / scale {worst:.3g}")
+
+
+def test_oracle_agrees_with_the_restatement_on_degenerate_and_large_frames():
+    frames = degenerate_frames()
+    assert len(frames) == 8
+    worst = 0.0
+    for kind, N, tpl, q in frames:
+        worst = max(worst, check_oracle_vs_restatement(tpl, q, 1000, 2.0, ctx=(kind, N)))
+        p, inl, _, ni = oracle.ransac_similarity(q, tpl)
+        assert not np.isnan(p).any(), (kind, N)
+        if kind == "mirrored_x":  # no similarity maps a mirrored frame onto the template
+            assert 2 <= ni < N // 2, (kind, N, ni)
+        else:
+            assert ni >= N // 2, (kind, N, ni)
+    tpl, q = large_frame()
+    assert len(q) == 1024
+    worst = max(worst, check_oracle_vs_restatement(tpl, q, 1000, 2.0, ctx="N1024"))
+    print(f"degenerate + N1024: max |dp| / scale {worst:.3g}")
+
+
+def test_oracle_entry_has_the_rigid_signature_and_no_model_cases():
+    L = oracle.lib()
+    assert L.kcmc_oracle_ransac_similarity.argtypes == L.kcmc_oracle_ransac_rigid.argtypes
+    # all frame points coincident: a == b == 0 in every trial, so no model (rank(A) == 0 in skimage)
+    p, inl, bt, ni = oracle.ransac_similarity(np.full((9, 2), 5.0), np.arange(18.0).reshape(9, 2))
+    assert np.isnan(p).all() and not inl.any() and bt == -1 and ni == 0
+    # dst = 2 R src + t exactly representable: the first trial wins with S == 0
+    q = np.array([[0.0, 0.0], [4.0, 0.0], [0.0, 8.0], [4.0, 8.0], [2.0, 2.0]])
+    p, inl, bt, ni = oracle.ransac_similarity(q, 2.0 * q[:, ::-1] * [-1.0, 1.0] + [3.0, -1.0])
+    assert inl.all() and bt == 0 and ni == 5
+    assert np.array_equal(p, [[0.0, -2.0, 3.0], [2.0, 0.0, -1.0]])
 
 
 def test_exact_set_is_exact_and_coincident_points_have_no_model():
