@@ -26,8 +26,9 @@
 // near-identity maps of motion correction) take a leaner form of the same path (mode 3,
 // fast_rows): scalar per-row origins from a per-frame table, immediate-offset taps, buffer
 // stores, and a per-tile choice of blend from the staged values (exact integer blend with
-// no range check when every value is < 16384; OpenCV's float blend on packed fp32 for
-// bright boxes).
+// no range check when every value is < 16384; with a few bright values the integer blend
+// and OpenCV's float blend only for rows with a sum near a rounding tie; the float blend on
+// packed fp32 for bright boxes).
 //
 // Two launches: warp_plan_kernel (one thread per tile) inverts the map in fp64 and
 // derives each tile's source box and the frame's row-origin table, so that the tile
@@ -299,6 +300,19 @@ __device__ __forceinline__ uint16_t round_q10(uint32_t S) {
   return (uint16_t)__float_as_uint(__builtin_fmaf((float)S, 0x1p-10f, 12582912.0f));
 }
 
+// Where rint(fl(S) / 1024) -- round_q10, or the fl(S) + 1.5 * 2^33 of the fast path -- can
+// differ from OpenCV's float blend, for the exact integer sum S = sum v_k K_k < 2^26.  Below
+// 2^24 both are exact.  From 2^24 on, each of OpenCV's four products and three partial sums
+// is below 2^26 and rounds by at most 2 (half an ulp of 4), so its float sum s3 is within
+// 4 * 2 + 3 * 2 = 14 of S, and fl(S) is within 2.  Two values within 14 of S = 1024 k + r
+// round to the same multiple of 1024 unless the tie 1024 k + 512 lies within 14 of S: only
+// pixels with S >= 2^24 and |r - 512| <= 14 need the float formula (33 of the 1024
+// residues at kTieWindow = 16).
+constexpr uint32_t kTieWindow = 16;  // >= the proven 14
+__device__ __forceinline__ bool near_tie(uint32_t S) {
+  return (S >> 24) != 0 && ((S - (512u - kTieWindow)) & 1023u) <= 2u * kTieWindow;
+}
+
 __device__ __forceinline__ uint32_t tap(const uint16_t* stile, int i) { return stile[i]; }
 
 // Bits 11-15 of v in one v_bfe_u32 (a shift and a mask otherwise).  The builtin, not inline
@@ -362,14 +376,21 @@ __device__ __forceinline__ f32x2 blend_float2(const uint32_t (&v)[2][4], const u
 enum FastBlend {
   kDark = 0,    // every staged value < 16384: S = sum v_k K_k < 2^24, so the exact separable
                 // integer evaluation of output_rows IS OpenCV's float result; no range check
-  kMixed = 1,   // some bright values: per output row (wave-uniform), the integer blend when
-                // all the row's taps are < 16384, blend_float2 otherwise
-  kBright = 2,  // bright regions over much of the box: blend_float2 throughout
+  kMixed = 1,   // few bright values: the integer blend for every row; the rows where some
+                // pixel's sum is near_tie (wave-uniform) are made again with blend_float2
+  kBright = 2,  // more bright values: blend_float2 throughout
 };
-// kBright above this fraction of bright staged chunks: a float row costs ~1.25x an integer
-// row, and a kMixed row pays ~10 % for its tap test (tools/warp_lab at config 2: dark
-// 2.85 ms, all-bright 3.56 ms).
-constexpr int kBrightShare = 3;  // bright chunks * kBrightShare > box chunks -> kBright
+// VALU instructions per wave row (counted in the gfx950 code): kDark 32; kMixed 34, 44 when
+// a sum is >= 2^24, and about 50 more when the row is made again; kBright 44.  So kMixed
+// pays while (rows made again) < (rows with no bright sum) / 5.  With b bright chunks in a
+// full 17 x 58 box: isolated hot pixels (one per chunk, <= 4 bright sums each, ~3 % of
+// them near_tie) touch 1 - exp(-2 b / 58) of the rows and remake about 0.002 b of them --
+// break-even near b = 35; a 32-px wide blob r rows high (b = 4 r) touches r + 1 rows and
+// remakes 0.67 r -- break-even near r = 15, b = 60.  Hence a twentieth of the box (49
+// chunks).  An earlier per-row choice by a test of the eight taps (41 / 53 VALU), kept
+// for boxes between that and a third bright, measured slower than kBright there: bright
+// taps then touch most rows (lab figures: DESIGN 4 K3).
+constexpr int kBrightShare = 20;  // bright chunks * kBrightShare > box chunks -> kBright
 
 // Output rows of a mode-3 tile, with the per-row overheads of output_rows removed: row
 // origins are scalar, the lower tap row is an immediate LDS offset, the store is a buffer
@@ -400,12 +421,8 @@ __device__ __forceinline__ void fast_rows(const uint16_t* stile, const int2* __r
   typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
   const u16x2 pitch2 = {(unsigned short)2, (unsigned short)(2 * kFastPitch)};
   const char* sbytes = reinterpret_cast<const char*>(stile);
-#pragma unroll
-  for (int i = 0; i < Cfg::kTileH / 4; ++i) {
-    const int y = yb + wave + 4 * i;  // wave-uniform
-    if (!INTERIOR && y >= H) break;
-    const uint32_t X0 = (uint32_t)(org[i].x - ox) << 6, Y0 = (uint32_t)(org[i].y - oy) << 6;  // scalar
-    uint32_t v[2][4], fx[2], fy[2];
+  // the lane's two pixels of a row with the scaled origin (X0, Y0): four taps and fractions each
+  auto row_taps = [&](uint32_t X0, uint32_t Y0, uint32_t(&v)[2][4], uint32_t(&fx)[2], uint32_t(&fy)[2]) {
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
       const uint32_t tX = X0 + ad6[p], tY = Y0 + bd6[p];
@@ -419,30 +436,60 @@ __device__ __forceinline__ void fast_rows(const uint16_t* stile, const int2* __r
       v[p][2] = t[kFastPitch];
       v[p][3] = t[kFastPitch + 1];
     }
-    bool use_float = BLEND == kBright;
-    if constexpr (BLEND == kMixed) {
-      const uint32_t taps = (v[0][0] | v[0][1] | v[0][2]) | (v[0][3] | v[1][0] | v[1][1]) | (v[1][2] | v[1][3]);
-      use_float = __builtin_amdgcn_ballot_w64((taps & 0xc000u) != 0) != 0;  // wave-uniform
-    }
+  };
+  auto store_row = [&](const f32x2& q, int y) {
+    const uint32_t out = __builtin_amdgcn_perm(__float_as_uint(q[1]), __float_as_uint(q[0]), 0x05040100u);
+    // aux 2 = nontemporal: the aligned frame is written once and not re-read here
+    if (store_ok) __builtin_amdgcn_raw_buffer_store_b32(out, dst_rsrc, xoff, 2 * y * W, 2);
+  };
+  uint32_t redo = 0;  // kMixed: bit i = the wave's row i waits for the float blend (scalar)
+#pragma unroll
+  for (int i = 0; i < Cfg::kTileH / 4; ++i) {
+    const int y = yb + wave + 4 * i;  // wave-uniform
+    if (!INTERIOR && y >= H) break;
+    const uint32_t X0 = (uint32_t)(org[i].x - ox) << 6, Y0 = (uint32_t)(org[i].y - oy) << 6;  // scalar
+    uint32_t v[2][4], fx[2], fy[2];
+    row_taps(X0, Y0, v, fx, fy);
     f32x2 q;
-    if (use_float) {
+    if constexpr (BLEND == kBright) {
       q = blend_float2(v, fx, fy);
     } else {
+      uint32_t Sp[2];
 #pragma unroll
       for (int p = 0; p < 2; ++p) {
         const uint32_t ax = 32 - fx[p], ay = 32 - fy[p];
         uint32_t h0 = __umul24(v[p][0], ax) + __umul24(v[p][1], fx[p]);
         uint32_t h1 = __umul24(v[p][2], ax) + __umul24(v[p][3], fx[p]);
         asm volatile("" : "+v"(h0), "+v"(h1));  // keep the separable form (see output_rows)
-        q[p] = (float)(__umul24(h0, ay) + __umul24(h1, fy[p]));
+        Sp[p] = __umul24(h0, ay) + __umul24(h1, fy[p]);
+        q[p] = (float)Sp[p];
       }
-      // rint(S / 1024) in the low bits: fl(S) + 1.5 * 2^33 rounds (half to even) to a
+      // rint(fl(S) / 1024) in the low bits: fl(S) + 1.5 * 2^33 rounds (half to even) to a
       // multiple of 1024, the float's unit in the last place there
       q += 0x1.8p33f;
+      if constexpr (BLEND == kMixed) {
+        // wave-uniform, two levels: rows with no sum >= 2^24 (most) pay one OR and one
+        // compare; of the others only those with a sum near a rounding tie are left out
+        // here and made by the float loop below (the row loop itself stays branch-lean)
+        if (__builtin_amdgcn_ballot_w64(((Sp[0] | Sp[1]) >> 24) != 0) != 0) {
+          if (__builtin_amdgcn_ballot_w64(((int)near_tie(Sp[0]) | (int)near_tie(Sp[1])) != 0) != 0) {
+            redo |= 1u << i;
+            continue;
+          }
+        }
+      }
     }
-    const uint32_t out = __builtin_amdgcn_perm(__float_as_uint(q[1]), __float_as_uint(q[0]), 0x05040100u);
-    // aux 2 = nontemporal: the aligned frame is written once and not re-read here
-    if (store_ok) __builtin_amdgcn_raw_buffer_store_b32(out, dst_rsrc, xoff, 2 * y * W, 2);
+    store_row(q, y);
+  }
+  if constexpr (BLEND == kMixed) {
+    while (redo) {  // the rows left out above (each written once, here): OpenCV's float blend
+      const int i = __builtin_ctz(redo);
+      redo &= redo - 1;
+      const int2 o = rt[i];
+      uint32_t v[2][4], fx[2], fy[2];
+      row_taps((uint32_t)(o.x - ox) << 6, (uint32_t)(o.y - oy) << 6, v, fx, fy);
+      store_row(blend_float2(v, fx, fy), yb + wave + 4 * i);
+    }
   }
 }
 
@@ -531,8 +578,8 @@ __device__ __forceinline__ uint32_t fastc_stage_land(uint16_t* stile, int gpr, i
 }
 
 // Output rows of a multi-channel mode-3 tile: fast_rows with C planes (same coordinate
-// scheme, same three blends, the blend decided once per tile or per row over every
-// channel's taps) and one b96 / b128 buffer store per lane and row.
+// scheme, same three blends, the blend decided once per tile and the rows to make again
+// over every channel's sums) and one b96 / b128 buffer store per lane and row.
 template <class Cfg, int C, int BLEND, bool INTERIOR>
 __device__ __forceinline__ void fastc_rows(const uint16_t* stile, const int2* __restrict__ rt, int ox, int oy,
                                            uint16_t* __restrict__ Dst, int H, int W, int xb, int yb, int wave,
@@ -554,12 +601,8 @@ __device__ __forceinline__ void fastc_rows(const uint16_t* stile, const int2* __
   typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
   const u16x2 pitch2 = {(unsigned short)2, (unsigned short)(2 * kPitch)};
   const char* sbytes = reinterpret_cast<const char*>(stile);
-#pragma unroll
-  for (int i = 0; i < Cfg::kTileH / 4; ++i) {
-    const int y = yb + wave + 4 * i;  // wave-uniform
-    if (!INTERIOR && y >= H) break;
-    const uint32_t X0 = (uint32_t)(org[i].x - ox) << 6, Y0 = (uint32_t)(org[i].y - oy) << 6;  // scalar
-    uint32_t v[C][2][4], fx[2], fy[2];
+  // the lane's two pixels of a row with the scaled origin (X0, Y0): C x four taps, fractions
+  auto row_taps = [&](uint32_t X0, uint32_t Y0, uint32_t(&v)[C][2][4], uint32_t(&fx)[2], uint32_t(&fy)[2]) {
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
       const uint32_t tX = X0 + ad6[p], tY = Y0 + bd6[p];
@@ -576,34 +619,9 @@ __device__ __forceinline__ void fastc_rows(const uint16_t* stile, const int2* __
         v[k][p][3] = t[k * kPlane + kPitch + 1];
       }
     }
-    bool use_float = BLEND == kBright;
-    if constexpr (BLEND == kMixed) {
-      uint32_t taps = 0;
-#pragma unroll
-      for (int k = 0; k < C; ++k)
-        taps |= (v[k][0][0] | v[k][0][1] | v[k][0][2]) | (v[k][0][3] | v[k][1][0] | v[k][1][1]) |
-                (v[k][1][2] | v[k][1][3]);
-      use_float = __builtin_amdgcn_ballot_w64((taps & 0xc000u) != 0) != 0;  // wave-uniform
-    }
-    f32x2 q[C];
-    if (use_float) {
-#pragma unroll
-      for (int k = 0; k < C; ++k) q[k] = blend_float2(v[k], fx, fy);
-    } else {
-#pragma unroll
-      for (int k = 0; k < C; ++k) {
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-          const uint32_t ax = 32 - fx[p], ay = 32 - fy[p];
-          uint32_t h0 = __umul24(v[k][p][0], ax) + __umul24(v[k][p][1], fx[p]);
-          uint32_t h1 = __umul24(v[k][p][2], ax) + __umul24(v[k][p][3], fx[p]);
-          asm volatile("" : "+v"(h0), "+v"(h1));  // keep the separable form (see output_rows)
-          q[k][p] = (float)(__umul24(h0, ay) + __umul24(h1, fy[p]));
-        }
-        q[k] += 0x1.8p33f;  // rint(S / 1024) in the low bits (fast_rows)
-      }
-    }
-    // the lane's 2 C channel values in interleaved order, two per dword
+  };
+  // the lane's 2 C channel values in interleaved order, two per dword
+  auto store_row = [&](const f32x2(&q)[C], int y) {
 #define KCMC_Q(px, ch) __float_as_uint(q[ch][px])
     if constexpr (C == 3) {
       typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
@@ -620,6 +638,63 @@ __device__ __forceinline__ void fastc_rows(const uint16_t* stile, const int2* __
       if (store_ok) __builtin_amdgcn_raw_buffer_store_b128(o, dst_rsrc, xoff, 2 * C * y * W, 2);
     }
 #undef KCMC_Q
+  };
+  uint32_t redo = 0;  // kMixed: bit i = the wave's row i waits for the float blend (scalar)
+#pragma unroll
+  for (int i = 0; i < Cfg::kTileH / 4; ++i) {
+    const int y = yb + wave + 4 * i;  // wave-uniform
+    if (!INTERIOR && y >= H) break;
+    const uint32_t X0 = (uint32_t)(org[i].x - ox) << 6, Y0 = (uint32_t)(org[i].y - oy) << 6;  // scalar
+    uint32_t v[C][2][4], fx[2], fy[2];
+    row_taps(X0, Y0, v, fx, fy);
+    f32x2 q[C];
+    if constexpr (BLEND == kBright) {
+#pragma unroll
+      for (int k = 0; k < C; ++k) q[k] = blend_float2(v[k], fx, fy);
+    } else {
+      uint32_t Sp[C][2], hi = 0;
+#pragma unroll
+      for (int k = 0; k < C; ++k) {
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+          const uint32_t ax = 32 - fx[p], ay = 32 - fy[p];
+          uint32_t h0 = __umul24(v[k][p][0], ax) + __umul24(v[k][p][1], fx[p]);
+          uint32_t h1 = __umul24(v[k][p][2], ax) + __umul24(v[k][p][3], fx[p]);
+          asm volatile("" : "+v"(h0), "+v"(h1));  // keep the separable form (see output_rows)
+          Sp[k][p] = __umul24(h0, ay) + __umul24(h1, fy[p]);
+          hi |= Sp[k][p];
+          q[k][p] = (float)Sp[k][p];
+        }
+        q[k] += 0x1.8p33f;  // rint(fl(S) / 1024) in the low bits (fast_rows)
+      }
+      if constexpr (BLEND == kMixed) {
+        // wave-uniform, two levels over every channel's sums; rows with a sum near a rounding
+        // tie are left to the float loop below (fast_rows)
+        if (__builtin_amdgcn_ballot_w64((hi >> 24) != 0) != 0) {
+          int tie = 0;
+#pragma unroll
+          for (int k = 0; k < C; ++k) tie |= (int)near_tie(Sp[k][0]) | (int)near_tie(Sp[k][1]);
+          if (__builtin_amdgcn_ballot_w64(tie != 0) != 0) {
+            redo |= 1u << i;
+            continue;
+          }
+        }
+      }
+    }
+    store_row(q, y);
+  }
+  if constexpr (BLEND == kMixed) {
+    while (redo) {  // the rows left out above (each written once, here): OpenCV's float blend
+      const int i = __builtin_ctz(redo);
+      redo &= redo - 1;
+      const int2 o = rt[i];
+      uint32_t v[C][2][4], fx[2], fy[2];
+      row_taps((uint32_t)(o.x - ox) << 6, (uint32_t)(o.y - oy) << 6, v, fx, fy);
+      f32x2 q[C];
+#pragma unroll
+      for (int k = 0; k < C; ++k) q[k] = blend_float2(v[k], fx, fy);
+      store_row(q, yb + wave + 4 * i);
+    }
   }
 }
 
@@ -697,8 +772,9 @@ __device__ __forceinline__ void output_rows(const uint16_t* stile, const Box& bo
       // Box-relative taps.  The blend is first evaluated exactly in integers,
       // S = ay*(v00*ax + v01*fx) + fy*(v10*ax + v11*fx) = sum v_k*K_k: while S < 2^24
       // every product and partial sum of OpenCV's float evaluation is an integer below
-      // 2^24 as well, hence exact, and its result is rint(S/1024).  Only pixels with
-      // S >= 2^24 (bright: taps beyond 14 bits) take the float-faithful blend.
+      // 2^24 as well, hence exact, and its result is rint(S/1024).  Of the pixels with
+      // S >= 2^24 (bright: taps beyond 14 bits) only those near a rounding tie (near_tie)
+      // take the float-faithful blend.
       uint32_t Sx[2 * C], hi = 0, fx[2], fy[2], li[2], v[2][C][4];
 #pragma unroll
       for (int p = 0; p < 2; ++p) {
@@ -738,7 +814,7 @@ __device__ __forceinline__ void output_rows(const uint16_t* stile, const Box& bo
         for (int p = 0; p < 2; ++p)
 #pragma unroll
           for (int k = 0; k < C; ++k)
-            if (Sx[p * C + k] >> 24)
+            if (near_tie(Sx[p * C + k]))
               o[p * C + k] = blend_int(v[p][k][0], v[p][k][1], v[p][k][2], v[p][k][3], fx[p], fy[p]);
       }
     } else {
@@ -1103,7 +1179,7 @@ __global__ __launch_bounds__(256) void persp_plan_kernel(const double* __restric
 }
 
 // remapBilinear's blend of four taps: exact integer evaluation, with the float-faithful
-// re-blend for sums >= 2^24 (see output_rows).
+// re-blend for sums >= 2^24 near a rounding tie (near_tie; see output_rows).
 __device__ __forceinline__ uint16_t blend_exact(uint32_t v00, uint32_t v01, uint32_t v10, uint32_t v11, int fx,
                                                 int fy) {
   const uint32_t ax = 32 - fx, ay = 32 - fy;
@@ -1112,7 +1188,7 @@ __device__ __forceinline__ uint16_t blend_exact(uint32_t v00, uint32_t v01, uint
   asm volatile("" : "+v"(h0), "+v"(h1));
   const uint32_t Sv = __umul24(h0, ay) + __umul24(h1, (uint32_t)fy);
   uint16_t r = round_q10(Sv);
-  if (Sv >> 24) r = blend_int(v00, v01, v10, v11, fx, fy);
+  if (near_tie(Sv)) r = blend_int(v00, v01, v10, v11, fx, fy);
   return r;
 }
 
