@@ -323,6 +323,40 @@ int kcmc_warp_perspective_u16(kcmc_ctx* ctx, const uint16_t* src_dev, uint16_t* 
                               const double* M_dev, int n_frames, int H, int W, int C, int inverse_map,
                               kcmc_stream_t stream);
 
+/* K3f: the piecewise-rigid field warp -- kcmc_warp_affine_u16 (grayscale, C = 1) with a smooth
+ * per-pixel residual source displacement added to the fixed-point source coordinate.  The
+ * reference has no such mode: the semantics are BUILD-DEFINED, in exact integer arithmetic,
+ * and pinned by a numpy restatement (tests/test_piecewise_host.py), not by a golden.
+ *   M_dev     [n_frames, 2, 3] f64   forward maps (or inverse maps with inverse_map != 0),
+ *                                    exactly as kcmc_warp_affine_u16 takes them
+ *   field_dev [n_frames, gy, gx, 2] i32   q: the residual displacement (x, y) at the nodes of
+ *                                    a gy x gx grid, in 1/1024 px; 1 <= gy, gx <= 16,
+ *                                    gy <= H, gx <= W.  Contract |q| <= 2^20: beyond it the
+ *                                    pixels are unspecified (never an out-of-bounds access).
+ * Node (i, j) sits at pixel-index coordinates cx_j = (j + 0.5) W / gx - 0.5,
+ * cy_i = (i + 0.5) H / gy - 0.5.  For output pixel (x, y):
+ *   X_aff, Y_aff: kcmc_warp_affine_u16's 1/1024-px coordinates adelta[x] + X0(y) (the same
+ *     inversion, the same cvRounds, the same + 16).
+ *   Along an axis of length L with g nodes, at pixel index p (integer divisions):
+ *     g == 1: k0 = 0, w = 0; otherwise
+ *     num = clamp((2p + 1) g - L, 0, 2L (g - 1)), k0 = min(num / (2L), g - 2),
+ *     w = ((num - k0 2L) 1024 + L) / (2L)   in [0, 1024]
+ *     (the field is held constant outside the outermost node centres).
+ *   (i0, wy) from (y, H, gy), (j0, wx) from (x, W, gx); per component, arithmetic shifts:
+ *     v_j = (q[i0][j] (1024 - wy) + q[i0 + 1][j] wy + 512) >> 10        (vertical first)
+ *     val = (v_j0 (1024 - wx) + v_{j0 + 1} wx + 512) >> 10              (then horizontal)
+ *     (a term with weight 0 is dropped: q[i0 + 1] / v_{j0 + 1} need not exist)
+ *   X = X_aff + val_x, Y = Y_aff + val_y; then kcmc_warp_affine_u16 again: integer part
+ *   sat_short(X >> 10), fraction (X >> 5) & 31, OpenCV's float blend, cvRound with
+ *   saturation, taps outside the image read 0, a frame whose map holds a NaN is zeros.
+ * So a field of equal nodes q moves every pixel by exactly q, and a zero field gives
+ * kcmc_warp_affine_u16's output bit for bit.  Asynchronous on `stream`, capturable under the
+ * affine warp's workspace rules; n_frames == 0 returns KCMC_OK; a NULL ctx or pointer,
+ * H or W < 1 or a grid outside the limits return KCMC_EINVAL before any device work. */
+int kcmc_warp_field_u16(kcmc_ctx* ctx, const uint16_t* src_dev, uint16_t* dst_dev, const double* M_dev,
+                        const int32_t* field_dev, int n_frames, int H, int W, int gy, int gx,
+                        int inverse_map, kcmc_stream_t stream);
+
 /* ------------------------------------------- f2: normalisation front end (VA:100-104)
  * brightest = np.percentile(images, 99.99) (VA:479-482) needs two order statistics of
  * the flattened uint16 stack; they come from two streaming 256-bin histogram passes:

@@ -155,6 +155,7 @@ def align_sharded(inp: _pl.SlabInputs, cfg: _pl.AlignConfig, group=None, impl: S
     exchanged bytes per rank do not grow with the number of frames on the other ranks."""
     if cfg.frame_downsample_rate != 1:
         raise ValueError("the sharded path requires frame_downsample_rate == 1 (frame_rate < 2*FRAME_SAMPLE_RATE)")
+    _pl.refuse_piecewise(cfg, "align_sharded")
     rank = dist.get_rank(group)
     dev = inp.kp_tpl.device
     n_local = inp.q_off.numel() - 1

@@ -116,6 +116,7 @@ def align_split(slabs: Sequence[_pl.SlabInputs], ranges: Sequence[SlabRange], cf
     affines / Euclidean transforms / skipped / interpolated lists of align_slab."""
     if len(slabs) != len(ranges) or not slabs:
         raise ValueError("align_split: one SlabRange per slab, at least one slab")
+    _pl.refuse_piecewise(cfg, "align_split")
     impl = impl or _hip_stages()
     n_tpl = slabs[0].des_tpl.shape[0]
     n_sample = ranges[-1].s1

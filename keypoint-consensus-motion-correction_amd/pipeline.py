@@ -43,6 +43,13 @@ class AlignConfig:
     # Opt-in (not the reference's matcher): BFMatcher norm, "l2" (the reference's
     # cv2.BFMatcher() default, VA:194) or "hamming" (NORM_HAMMING for binary descriptors).
     match_norm: str = "l2"
+    # Opt-in (build-defined, kcmc_amd.piecewise): piecewise-rigid correction on a (gy, gx) grid of
+    # nodes -- per-cell rigid RANSAC on the sample frames and the field warp instead of the
+    # affine warp.  None: off, nothing new runs.  align_slab only.
+    piecewise_grid: Optional[Tuple[int, int]] = None
+    piecewise_window: float = 1.0        # PIECEWISE_WINDOW: a cell's half window in cell sizes
+    piecewise_min_points: int = 6        # PIECEWISE_MIN_POINTS: fewer points, no cell fit
+    piecewise_max_residual: float = 8.0  # PIECEWISE_MAX_RESIDUAL: px, larger residuals are dropped
 
     @property
     def effective_frame_skip(self) -> int:
@@ -304,10 +311,47 @@ def align_slab(inp: SlabInputs, cfg: AlignConfig, logger: Optional[logging.Logge
     rr = ransac_stage(match, inp.kp_tpl, cons, cfg)
     params = rr.params.cpu().numpy()
     affines, skipped, interpolated, eu = postprocess_affines(params, cfg)
-    aligned = warp_stage(inp.frames, affines, out=out)
+    extras = {}
+    if cfg.piecewise_grid is not None:
+        aligned, extras = piecewise_stage(inp, cfg, match, cons, params, affines, out=out)
+    else:
+        aligned = warp_stage(inp.frames, affines, out=out)
     return SlabResult(aligned, affines, eu, skipped, interpolated,
                       match if keep_intermediates else None, cons if keep_intermediates else None,
-                      rr if keep_intermediates else None, counts)
+                      rr if keep_intermediates else None, counts, extras)
+
+
+def refuse_piecewise(cfg: AlignConfig, where: str) -> None:
+    """The paths that do not run the piecewise-rigid mode say so instead of ignoring the grid."""
+    if cfg.piecewise_grid is not None:
+        raise NotImplementedError(f"piecewise_grid is not supported by {where} (align_slab on one device only)")
+
+
+def piecewise_stage(inp: SlabInputs, cfg: AlignConfig, match: stages.MatchResult, cons: stages.Consensus,
+                    params: np.ndarray, affines: np.ndarray, out: Optional[torch.Tensor] = None):
+    """The piecewise-rigid tail of align_slab (kcmc_amd.piecewise): per-cell rigid fits of the
+    sample frames after the global RANSAC, the residual field of every frame, the field warp.
+    Returns (aligned, extras) with extras' patch_residuals [F, gy, gx, 2] px, patch_points and
+    patch_fitted [n_sample, gy, gx]."""
+    from . import piecewise as _pw
+
+    if cfg.ransac_model == "projective":
+        raise NotImplementedError("piecewise_grid does not support ransac_model = 'projective'")
+    if inp.frames.dim() != 3:
+        raise NotImplementedError("piecewise_grid supports grayscale stacks [F, H, W] only")
+    F, H, W = inp.frames.shape
+    grid = _pw.check_grid(cfg.piecewise_grid, H, W)
+    _pw.check_options(cfg.piecewise_min_points, cfg.piecewise_window, cfg.piecewise_max_residual)
+    fits = _pw.fit_cells(match.kp_ordered, inp.kp_tpl, cons.pt_off_dev, cons.pt_idx_dev, cons.pt_off, params, H, W,
+                         grid, window=cfg.piecewise_window, min_points=int(cfg.piecewise_min_points),
+                         trials=cfg.ransac_trials, residual_threshold=cfg.ransac_threshold, seed=cfg.seed,
+                         spatial_rate=cfg.spatial_rate)
+    q = _pw.fields_from_fits(fits, params, F, cfg.frame_downsample_rate, H, W, grid, cfg.piecewise_max_residual)
+    dev = inp.frames.device
+    maps = torch.from_numpy(np.ascontiguousarray(affines[:F], dtype=np.float64)).to(dev)
+    aligned = stages.warp_field_u16(inp.frames, maps, torch.from_numpy(q).to(dev), out=out)
+    return aligned, {"patch_residuals": q.astype(np.float64) / 1024.0, "patch_points": fits.points,
+                     "patch_fitted": fits.fitted, "patch_fits": fits}
 
 
 def _d2h_async(t: torch.Tensor, copy: torch.cuda.Stream,
@@ -429,6 +473,7 @@ class OverlappedSlabs:
     def __init__(self, device, cfg: AlignConfig, logger: Optional[logging.Logger] = None,
                  counts: Optional[List[int]] = None, group=None, match_beside: bool = False):
         self.match_beside = bool(match_beside)
+        refuse_piecewise(cfg, "OverlappedSlabs")
         if counts is not None and len(counts) > 1 and cfg.frame_downsample_rate != 1:
             # the rank's first frame is counted in sample frames, the affines in full-rate
             # frames: the same restriction as distributed.align_sharded
@@ -777,6 +822,7 @@ def align_streamed(frames_host: torch.Tensor, inp: SlabInputs, cfg: AlignConfig,
     copy of slab k+1, warp of slab k and device->host copy of slab k-1 overlap, so the
     rate is bound by PCIe (both directions) rather than HBM.  Returns
     (out_host, SlabResult without the aligned tensor)."""
+    refuse_piecewise(cfg, "align_streamed")
     dev = inp.des_tpl.device
     F = frames_host.shape[0]
     if out_host is None:

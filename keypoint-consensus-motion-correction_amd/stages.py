@@ -702,6 +702,41 @@ def warp_perspective_u16(frames: torch.Tensor, homographies: torch.Tensor, out: 
     return out
 
 
+def warp_field_u16(frames: torch.Tensor, affines: torch.Tensor, field_q: torch.Tensor,
+                   out: Optional[torch.Tensor] = None, stream: Optional[int] = None,
+                   inverse_map: bool = False) -> torch.Tensor:
+    """The piecewise-rigid field warp (K3f, build-defined: include/kcmc.h): warp_affine_u16 with
+    the residual displacement field_q [F, gy, gx, 2] int32 (x, y in 1/1024 px at the nodes of a
+    gy x gx grid) interpolated over the frame and added to the source coordinate.
+
+    frames [F, H, W] uint16 on the device (grayscale only); affines [F, 2, 3] f64.
+    """
+    dev = _device_of(frames)
+    if frames.dtype != torch.uint16:
+        raise TypeError(f"frames: expected torch.uint16, got {frames.dtype}")
+    if frames.dim() != 3:
+        raise ValueError("frames must be [F, H, W] (the field warp is grayscale only)")
+    _require(frames, "frames", torch.uint16, dev)
+    _require(affines, "affines", torch.float64, dev, 3)
+    _require(field_q, "field_q", torch.int32, dev, 4)
+    F, H, W = frames.shape
+    if affines.shape != (F, 2, 3):
+        raise ValueError(f"affines must be [{F}, 2, 3], got {tuple(affines.shape)}")
+    if field_q.shape[0] != F or field_q.shape[3] != 2:
+        raise ValueError(f"field_q must be [{F}, gy, gx, 2], got {tuple(field_q.shape)}")
+    gy, gx = int(field_q.shape[1]), int(field_q.shape[2])
+    if out is None:
+        out = torch.empty_like(frames)
+    else:
+        _require(out, "out", torch.uint16, dev)
+        if out.shape != frames.shape:
+            raise ValueError("out must have the shape of frames")
+    L = _lib.load()
+    _lib.check(L.kcmc_warp_field_u16(_ctx(dev).handle, _ptr(frames), _ptr(out), _ptr(affines), _ptr(field_q), F, H, W,
+                                     gy, gx, int(bool(inverse_map)), _stream(dev, stream)))
+    return out
+
+
 def _warp_shape(frames_shape) -> Tuple[int, int, int, int]:
     if len(frames_shape) not in (3, 4):
         raise ValueError("frames must be [F, H, W] or [F, H, W, C]")

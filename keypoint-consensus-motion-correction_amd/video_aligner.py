@@ -31,6 +31,7 @@ import torch
 
 from . import affines as _aff
 from . import multidevice as _md
+from . import piecewise as _pw
 from . import pipeline as _pl
 from . import quality as _q
 from . import stages
@@ -140,6 +141,19 @@ class VideoAligner:
     # detection and keypoints are reused; only the template is detected again.
     TEMPLATE_REFINE_ITERS = 0
     TEMPLATE_REFINE_TOP_FRAC = 0.5
+    # New (opt-in, kcmc_amd.piecewise; build-defined, the reference has no such mode):
+    # piecewise-rigid correction.  (gy, gx), each in [1, 16]: after the global RANSAC every sample
+    # frame fits one rigid model per grid cell from the consensus points in the cell's window
+    # (PIECEWISE_WINDOW cell sizes to each side; cells with fewer than PIECEWISE_MIN_POINTS
+    # points have none), the residual of each accepted cell model against the global map at
+    # the cell's node (dropped above PIECEWISE_MAX_RESIDUAL px) becomes a displacement field,
+    # and the frames are made by the field warp (affines, the transform summary and the
+    # skipped list stay what they are without the grid).  Results: patch_residuals,
+    # patch_points, patch_fitted.  Grayscale stacks, first device only.
+    PIECEWISE_GRID: Optional[Tuple[int, int]] = None
+    PIECEWISE_WINDOW = 1.0
+    PIECEWISE_MIN_POINTS = 6
+    PIECEWISE_MAX_RESIDUAL = 8.0
 
     def __init__(self, logger: LoggerAdapter = None):
         self.logger = logger
@@ -150,13 +164,15 @@ class VideoAligner:
         self.interpolated_idxs = None
         self._kp_template = None
         self._des_template = None
+        self._logged_one_device = False
         self._reset_quality()
+        self._reset_piecewise()
 
     # ------------------------------------------------------------------ helpers
     @classmethod
-    def _devices(cls) -> List[int]:
-        """The devices of the hot path: DEVICES, else [DEVICE], else every visible device
-        with the current one first."""
+    def _all_devices(cls) -> List[int]:
+        """The configured devices: DEVICES, else [DEVICE], else every visible device with the
+        current one first."""
         if not torch.cuda.is_available():
             from ._lib import KcmcLibraryError
 
@@ -172,6 +188,13 @@ class VideoAligner:
         return [cur] + [d for d in _md.visible_devices() if d != cur]
 
     @classmethod
+    def _devices(cls) -> List[int]:
+        """The devices of the hot path (_all_devices); the first one only with PIECEWISE_GRID
+        (the piecewise-rigid mode runs on one device in this version)."""
+        devs = cls._all_devices()
+        return devs[:1] if cls.PIECEWISE_GRID is not None else devs
+
+    @classmethod
     def _device(cls) -> torch.device:
         return torch.device("cuda", cls._devices()[0])
 
@@ -184,7 +207,46 @@ class VideoAligner:
             ransac_threshold=float(cls.RANSAC_RESIDUAL_THRESH), ransac_min_samples=cls.RANSAC_MIN_SAMPLES,
             seed=cls.RANDOM_SEED, spatial_rate=cls.SPATIAL_DOWNSAMPLE_RATE,
             frame_downsample_rate=int(frame_downsample_rate), ransac_model=cls.RANSAC_MODEL,
-            match_norm=cls.MATCH_NORM)
+            match_norm=cls.MATCH_NORM,
+            piecewise_grid=None if cls.PIECEWISE_GRID is None else _pw.check_grid(cls.PIECEWISE_GRID),
+            piecewise_window=float(cls.PIECEWISE_WINDOW), piecewise_min_points=int(cls.PIECEWISE_MIN_POINTS),
+            piecewise_max_residual=float(cls.PIECEWISE_MAX_RESIDUAL))
+
+    # ------------------------------------------------------------- piecewise-rigid correction
+    def _reset_piecewise(self) -> None:
+        self.patch_residuals = None
+        self.patch_points = None
+        self.patch_fitted = None
+
+    def _piecewise_on(self, images=None) -> bool:
+        """Whether the piecewise-rigid mode runs, after the checks that must fail before any
+        work (``images``: only its number of dimensions is read, when it has one)."""
+        if self.PIECEWISE_GRID is None:
+            return False
+        _pw.check_grid(self.PIECEWISE_GRID)
+        _pw.check_options(self.PIECEWISE_MIN_POINTS, self.PIECEWISE_WINDOW, self.PIECEWISE_MAX_RESIDUAL)
+        if self.RANSAC_MODEL == "projective":
+            raise NotImplementedError("PIECEWISE_GRID does not support RANSAC_MODEL = 'projective' (the field "
+                                      "warp adds its displacement to an affine source coordinate)")
+        if bool(self.QUALITY_METRICS) or int(self.TEMPLATE_REFINE_ITERS) > 0:
+            raise NotImplementedError("PIECEWISE_GRID does not run together with QUALITY_METRICS / "
+                                      "TEMPLATE_REFINE_ITERS (the valid region of a field warp is not defined yet)")
+        if getattr(images, "ndim", 3) != 3:
+            raise NotImplementedError("PIECEWISE_GRID supports grayscale stacks [F, H, W] only")
+        return True
+
+    def _log_one_device(self) -> None:
+        if self.PIECEWISE_GRID is not None and not self._logged_one_device and len(self._all_devices()) > 1:
+            self._logged_one_device = True
+            self.logger.info(f"PIECEWISE_GRID: the piecewise-rigid mode runs on device {self._devices()[0]} only")
+
+    def _take_piecewise(self, res) -> None:
+        ex = getattr(res, "extras", None) or {}
+        self.patch_residuals = ex.get("patch_residuals")
+        self.patch_points = ex.get("patch_points")
+        self.patch_fitted = ex.get("patch_fitted")
+        if self.patch_residuals is not None:  # the maps the field was added to
+            self.affines = res.affines
 
     # ------------------------------------------------- quality metrics, template refinement
     def _reset_quality(self) -> None:
@@ -288,6 +350,9 @@ class VideoAligner:
         """
         self._reset_quality()
         self._quality_on()
+        self._reset_piecewise()
+        self._piecewise_on(images)
+        self._log_one_device()
         self.logger.info(f"aligning {len(images)} frames with n_kp_global: {n_kp_global} and {detector_algorithm}")
         if not 0 <= self.TEMPLATE_FRAME_LOC <= 1:
             raise ValueError("`template_frame_loc` must be between 0 and 1")
@@ -487,6 +552,9 @@ class VideoAligner:
         and uint8 descriptors [n, D]; template keypoints/descriptors likewise."""
         self._reset_quality()
         self._quality_on(refine_supported=False)
+        self._reset_piecewise()
+        self._piecewise_on(images)
+        self._log_one_device()
         self._kp_template = np.asarray(kp_template, dtype=np.float64).reshape(-1, 2)
         self._des_template = np.asarray(des_template, dtype=np.uint8)
         rate = max(1, frame_rate // self.FRAME_SAMPLE_RATE)
@@ -525,6 +593,7 @@ class VideoAligner:
                                detect_template)
         self.interpolated_idxs = res.interpolated
         self.logger.info(f"aligned frames in: {round(time.time() - t_start)} s")
+        self._take_piecewise(res)
         aligned = res.aligned
         if patch is not None:
             x_start, y_start, width, height = patch
