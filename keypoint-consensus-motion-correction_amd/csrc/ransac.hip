@@ -93,28 +93,6 @@ __device__ __forceinline__ double resid2(const Model& m, const Pts& P, int k, do
   return r * r;
 }
 
-// numpy pairwise_sum over residual^2 of points [start, start+n) for n <= 128:
-// n < 8 sequential, else 8 strided accumulators + sequential remainder.
-__device__ __forceinline__ double pw_leaf(const Model& m, const Pts& P, int start, int n, double thresh, int& cnt) {
-  if (n < 8) {
-    double res = 0.0;
-    for (int i = 0; i < n; ++i) res += resid2(m, P, start + i, thresh, cnt);
-    return res;
-  }
-  double r[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = resid2(m, P, start + j, thresh, cnt);
-  int i = 8;
-  const int nfull = n - (n % 8);
-  for (; i < nfull; i += 8) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] += resid2(m, P, start + i + j, thresh, cnt);
-  }
-  double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-  for (; i < n; ++i) res += resid2(m, P, start + i, thresh, cnt);
-  return res;
-}
-
 // Phase A of the scoring (see the kernel): the inlier count through the squared
 // distance (r < thresh <=> q < tq, tq = the smallest double whose correctly rounded root
 // is >= thresh; the q of every point is computed exactly as resid2 computes it) and an
@@ -149,32 +127,16 @@ __device__ __forceinline__ void ransac_rigid_frame(
     uint8_t* __restrict__ out_inl, int32_t* __restrict__ out_nin, int32_t* __restrict__ out_best) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   __shared__ double red[kThreads / 64 * 8];
-  __shared__ int s_cnt[kThreads / 64];
-  __shared__ double s_min[kThreads / 64];
-  __shared__ int s_best[kThreads / 64 * 2];
-  __shared__ double s_bestS[kThreads / 64];
+  __shared__ Scratch sc;
   __shared__ int s_any_zero;
-  __shared__ int s_final_t;
   __shared__ Plan s_plan;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
-  const int p0 = pt_off[f];
-  const int N = pt_off[f + 1] - p0;
-
-  const bool skip_frame = N < n_skip || N < 3 || N > kMaxN;
-  const int hoff = (!skip_frame && N < hyp_off_len) ? hyp_off[N] : -1;
-  const bool nan_frame = skip_frame || hoff < 0;
-  if (LARGE != (!nan_frame && N > 128)) return;  // the other launch owns this frame
-  if (nan_frame) {
-    if (tid < 6) out_params[6 * (size_t)f + tid] = NAN;
-    for (int k = tid; k < N; k += kThreads) out_inl[p0 + k] = 0;
-    if (tid == 0) {
-      out_nin[f] = skip_frame ? 0 : -1;  // -1: no hypothesis table was prepared for N
-      out_best[f] = -1;
-    }
+  int p0, N, hoff;
+  if (!frame_begin<LARGE, 6>(f, pt_off, n_skip, 3, hyp_off, hyp_off_len, out_params, out_inl, out_nin, out_best, p0, N,
+                             hoff))
     return;
-  }
   const uint32_t* H = hyp + hoff;
 
   // LDS: sx, sy, dx, dy [N] f64 | the points as (x, y, u, v) [N] f32x4 | trial S (low bound)
@@ -197,18 +159,7 @@ __device__ __forceinline__ void ransac_rigid_frame(
   }
 
   auto gather = [&](int k, double (&c)[4]) {
-    size_t si, di;
-    if (pt_idx) {
-      const int q = pt_idx[p0 + k];
-      si = (size_t)f * src_stride + q;
-      di = (size_t)q;
-    } else {
-      si = di = (size_t)(p0 + k);
-    }
-    c[0] = src[2 * si];
-    c[1] = src[2 * si + 1];
-    c[2] = dst[2 * di];
-    c[3] = dst[2 * di + 1];
+    gather_point(src, dst, pt_idx, src_stride, f, p0 + k, c[0], c[1], c[2], c[3]);
   };
   if (tid == 0) s_any_zero = 0;
   __shared__ Mag mg;
@@ -259,6 +210,11 @@ __device__ __forceinline__ void ransac_rigid_frame(
   }
 
   const Pts P{sx, sy, dxs, dys};
+  auto fit_of = [&](int t) {  // trial t's model from its sample pair
+    const uint32_t pr = H[t];
+    const int i = (int)(pr & 0xffffu), j = (int)(pr >> 16);
+    return fit2<SCALE>(sx[i], sy[i], sx[j], sy[j], dxs[i], dys[i], dxs[j], dys[j]);
+  };
 
   // ---- phase A: every trial's inlier count and a bracket [tS, tSh] of its S.  In fp32
   // (ransac_common.h score32: certain inliers, outliers and the undecided points between
@@ -275,9 +231,7 @@ __device__ __forceinline__ void ransac_rigid_frame(
     int mlo = -1;
     bool deferred = false;  // trials the fp32 bound cannot take: the fp64 loop below
     for (int t = tid; t < T; t += kThreads) {
-      const uint32_t pr = H[t];
-      const int i = (int)(pr & 0xffffu), j = (int)(pr >> 16);
-      const Model m = fit2<SCALE>(sx[i], sy[i], sx[j], sy[j], dxs[i], dys[i], dxs[j], dys[j]);
+      const Model m = fit_of(t);
       int v = -1;
       double slo = NAN, shi = NAN;
       Lin32 L;
@@ -299,9 +253,7 @@ __device__ __forceinline__ void ransac_rigid_frame(
     if (deferred) {
       for (int t = tid; t < T; t += kThreads) {
         if (tC[t] != INT_MIN) continue;
-        const uint32_t pr = H[t];
-        const int i = (int)(pr & 0xffffu), j = (int)(pr >> 16);
-        const Model m = fit2<SCALE>(sx[i], sy[i], sx[j], sy[j], dxs[i], dys[i], dxs[j], dys[j]);
+        const Model m = fit_of(t);
         int cnt = 0;
         const float S32 = score_fast(m, P, N, tq, cnt);
         double slo, shi;
@@ -313,206 +265,84 @@ __device__ __forceinline__ void ransac_rigid_frame(
         mlo = max(mlo, cnt);
       }
     }
-    for (int o = 32; o > 0; o >>= 1) {
-      mlo = max(mlo, __shfl_xor(mlo, o));
-      flag |= __shfl_xor(flag, o);
-    }
-    if (lane == 0) s_cnt[wave] = (mlo + 1) | (flag << 30);  // counts <= kMaxN
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < kThreads / 64; ++w) {
-      const int v = s_cnt[w];
-      flag |= v >> 30;
-      mlo = max(mlo, (v & 0x3fffffff) - 1);
-    }
-    __syncthreads();  // s_cnt is reused
+    block_max_flag(mlo, flag, sc.cnt);
+    __syncthreads();  // sc.cnt is reused
     // phase A2: the exact count of every trial the undecided points could lift to mlo, each
     // by a whole wave (the points over the lanes, fp64 as score_fast computes them)
-    for (int t0 = wave * 64; t0 < T; t0 += kThreads) {
-      const int t = t0 + lane;
-      uint64_t need = __ballot(!flag && t < T && und_of(tC[t]) > 0 && cnt_of(tC[t]) + und_of(tC[t]) >= mlo);
-      while (need) {
-        const int tc = t0 + __builtin_ctzll(need);
-        need &= need - 1;
-        const uint32_t pr = H[tc];
-        const int i = (int)(pr & 0xffffu), j = (int)(pr >> 16);
-        const Model m = fit2<SCALE>(sx[i], sy[i], sx[j], sy[j], dxs[i], dys[i], dxs[j], dys[j]);
-        int c = 0;
-        double sq = 0.0;
-        for (int k = lane; k < N; k += 64) {
-          const double x = sx[k], y = sy[k];
-          const double xp = fma(y, -m.s, x * m.c) + m.tx;
-          const double yp = fma(y, m.c, x * m.s) + m.ty;
-          const double ex = xp - dxs[k], ey = yp - dys[k];
-          const double q = ex * ex + ey * ey;
-          c += (q < tq) ? 1 : 0;
-          sq += q;
-        }
-        c = wave_sum_i(c);
-        double slo, shi;
-        sd_bracket(wave_sum(sq), N, slo, shi);
-        if (!(slo >= 1e-30 && shi <= 1e30)) flag = 1;
-        if (lane == 0) {
-          tC[tc] = c;
-          tS[tc] = slo;
-          tSh[tc] = shi;
-        }
-      }
-    }
+    for_each_wave_trial(
+        T, [&](int t) { return !flag && und_of(tC[t]) > 0 && cnt_of(tC[t]) + und_of(tC[t]) >= mlo; },
+        [&](int tc) {
+          const Model m = fit_of(tc);
+          int c = 0;
+          double sq = 0.0;
+          for (int k = lane; k < N; k += 64) {
+            const double x = sx[k], y = sy[k];
+            const double xp = fma(y, -m.s, x * m.c) + m.tx;
+            const double yp = fma(y, m.c, x * m.s) + m.ty;
+            const double ex = xp - dxs[k], ey = yp - dys[k];
+            const double q = ex * ex + ey * ey;
+            c += (q < tq) ? 1 : 0;
+            sq += q;
+          }
+          c = wave_sum_i(c);
+          double slo, shi;
+          sd_bracket(wave_sum(sq), N, slo, shi);
+          if (!(slo >= 1e-30 && shi <= 1e30)) flag = 1;
+          if (lane == 0) {
+            tC[tc] = c;
+            tS[tc] = slo;
+            tSh[tc] = shi;
+          }
+        });
     __syncthreads();  // the A2 results of the other waves' lanes
     for (int t = tid; t < T; t += kThreads) mcount = max(mcount, cnt_of(tC[t]));
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    mcount = max(mcount, __shfl_xor(mcount, o));
-    flag |= __shfl_xor(flag, o);
-  }
-  if (lane == 0) s_cnt[wave] = (mcount + 1) | (flag << 30);  // counts <= kMaxN
-  __syncthreads();
-#pragma unroll
-  for (int w = 0; w < kThreads / 64; ++w) {
-    const int v = s_cnt[w];
-    flag |= v >> 30;
-    mcount = max(mcount, (v & 0x3fffffff) - 1);
-  }
+  block_max_flag(mcount, flag, sc.cnt);
   const bool exact = flag != 0 || mcount <= 0;
 
-  int bc = -1, bt = INT_MAX;
-  double bS = INFINITY;
+  Best best;
   bool any_zero = false;
   if (exact) {
-    for (int t = tid; t < T; t += kThreads) {
-      const uint32_t pr = H[t];
-      const int i = (int)(pr & 0xffffu), j = (int)(pr >> 16);
-      const Model m = fit2<SCALE>(sx[i], sy[i], sx[j], sy[j], dxs[i], dys[i], dxs[j], dys[j]);
-      int cnt = 0;
-      double S = NAN;
-      if (m.ok) {
-        if (!LARGE) {
-          S = pw_leaf(m, P, 0, N, thresh, cnt);
-        } else {
-          int sp = 0;
-          for (int l = 0; l < s_plan.n; ++l) {
-            stk[sp++ * kThreads + tid] = pw_leaf(m, P, s_plan.start[l], s_plan.len[l], thresh, cnt);
-            for (int c = s_plan.pops[l]; c > 0; --c) {
-              const double b = stk[--sp * kThreads + tid];
-              const double a = stk[(sp - 1) * kThreads + tid];
-              stk[(sp - 1) * kThreads + tid] = a + b;
-            }
-          }
-          S = stk[tid];
-        }
-      }
-      tS[t] = S;
-      tC[t] = cnt;
-      const bool valid = !isnan(S) && (cnt > 0 || S < INFINITY);
-      if (valid) {
-        if (S <= 0.0) any_zero = true;
-        if (better(cnt, S, t, bc, bS, bt)) {
-          bc = cnt;
-          bS = S;
-          bt = t;
-        }
-      }
-    }
+    exact_trials(
+        T,
+        [&](int t, int& cnt) {
+          const Model m = fit_of(t);
+          if (!m.ok) return (double)NAN;
+          return thread_pairwise<LARGE>([&](int k) { return resid2(m, P, k, thresh, cnt); }, N, s_plan, stk, tid);
+        },
+        tS, tC, best, any_zero);
   } else {
     double lm = INFINITY;
     for (int t = tid; t < T; t += kThreads)
       if (cnt_of(tC[t]) == mcount) lm = fmin(lm, tSh[t]);
-    for (int o = 32; o > 0; o >>= 1) lm = fmin(lm, __shfl_xor(lm, o));
-    if (lane == 0) s_min[wave] = lm;
-    __syncthreads();
-    const double minhi = fmin(fmin(s_min[0], s_min[1]), fmin(s_min[2], s_min[3]));
+    const double minhi = block_min(lm, sc.min);
     double* vals = wvals + wave * 128;
     double* wstk = stk + wave * kMaxStack;  // LARGE: the wave's combine stack (uniform values)
-    // phase B: this wave's candidate trials (t = t0 + lane), each scored by the whole wave
-    for (int t0 = wave * 64; t0 < T; t0 += kThreads) {
-      const int t = t0 + lane;
-      uint64_t cand = __ballot(t < T && cnt_of(tC[t]) == mcount && tS[t] <= minhi);
-      while (cand) {
-        const int tc = t0 + __builtin_ctzll(cand);
-        cand &= cand - 1;
-        const uint32_t pr = H[tc];
-        const int i = (int)(pr & 0xffffu), j = (int)(pr >> 16);
-        const Model m = fit2<SCALE>(sx[i], sy[i], sx[j], sy[j], dxs[i], dys[i], dxs[j], dys[j]);
-        const double S = wave_pairwise<LARGE>(
-            [&](int k) {
-              int c = 0;
-              return resid2(m, P, k, thresh, c);
-            },
-            N, s_plan, vals, wstk, lane);
-        if (!isnan(S) && better(mcount, S, tc, bc, bS, bt)) {  // wave-uniform
-          bc = mcount;
-          bS = S;
-          bt = tc;
-        }
-      }
-    }
+    // phase B: this wave's candidate trials, each scored by the whole wave
+    for_each_wave_trial(
+        T, [&](int t) { return cnt_of(tC[t]) == mcount && tS[t] <= minhi; },
+        [&](int tc) {
+          const Model m = fit_of(tc);
+          const double S = wave_pairwise<LARGE>(
+              [&](int k) {
+                int c = 0;
+                return resid2(m, P, k, thresh, c);
+              },
+              N, s_plan, vals, wstk, lane);
+          if (!isnan(S)) best.take(mcount, S, tc);  // wave-uniform
+        });
   }
-  // workgroup argmax of (count, -S, -t)
-  for (int o = 32; o > 0; o >>= 1) {
-    const int oc = __shfl_xor(bc, o);
-    const double oS = __shfl_xor(bS, o);
-    const int ot = __shfl_xor(bt, o);
-    if (better(oc, oS, ot, bc, bS, bt)) {
-      bc = oc;
-      bS = oS;
-      bt = ot;
-    }
-  }
-  if (lane == 0) {
-    s_best[2 * wave] = bc;
-    s_best[2 * wave + 1] = bt;
-    s_bestS[wave] = bS;
-  }
-  if (any_zero) atomicOr(&s_any_zero, 1);
-  __syncthreads();
-  if (tid == 0) {
-    int fc = -1, ft = INT_MAX;
-    double fS = INFINITY;
-    for (int w = 0; w < kThreads / 64; ++w)
-      if (better(s_best[2 * w], s_bestS[w], s_best[2 * w + 1], fc, fS, ft)) {
-        fc = s_best[2 * w];
-        fS = s_bestS[w];
-        ft = s_best[2 * w + 1];
-      }
-    if (s_any_zero) {
-      // skimage stops as soon as the running best has S <= 0 (fit.py:862-869):
-      // replay the trial sequence to find where it stopped.
-      int c0 = 0, t0 = -1;
-      double S0 = INFINITY;
-      for (int t = 0; t < T; ++t) {
-        const double S = tS[t];
-        const int c = tC[t];
-        if (isnan(S)) continue;
-        if (c > c0 || (c == c0 && S < S0)) {
-          c0 = c;
-          S0 = S;
-          t0 = t;
-          if (S0 <= 0.0) break;
-        }
-      }
-      ft = t0;
-      fc = c0;
-    }
-    s_final_t = (ft == INT_MAX) ? -1 : ft;
-  }
-  __syncthreads();
-  const int best_t = s_final_t;
+  int best_t, best_c;
+  select_best(best, any_zero, T, tS, tC, sc, s_any_zero, best_t, best_c);
 
   // inlier mask of the best hypothesis (same arithmetic as the scoring loop)
-  int nin_local = 0;
   Model bm{0, 0, 0, 0, false};
-  if (best_t >= 0) {
-    const uint32_t pr = H[best_t];
-    const int i = (int)(pr & 0xffffu), j = (int)(pr >> 16);
-    bm = fit2<SCALE>(sx[i], sy[i], sx[j], sy[j], dxs[i], dys[i], dxs[j], dys[j]);
-  }
+  if (best_t >= 0) bm = fit_of(best_t);
   for (int k = tid; k < N; k += kThreads) {
     int c = 0;
     if (bm.ok) resid2(bm, P, k, thresh, c);
     inl[k] = (uint8_t)c;
     out_inl[p0 + k] = (uint8_t)c;
-    nin_local += c;
   }
   __syncthreads();
   // refit on the inliers (skimage fit.py:871-875 -> _umeyama over d[best_inliers])
@@ -605,23 +435,18 @@ __device__ __forceinline__ void ransac_rigid_frame(
     out_nin[f] = (int32_t)n_in;
     out_best[f] = best_t;
   }
-  (void)nin_local;
 }
 
-// Workgroup g scores frames g, g + grid, ... (the product launches one workgroup per frame;
-// narrower grids measured slower beside the warp).
+// One workgroup per frame.
 template <bool LARGE, bool SCALE>
 __global__ __launch_bounds__(kThreads, 4) void ransac_rigid_kernel(
-    int n_frames, const double* __restrict__ src, const double* __restrict__ dst, const int32_t* __restrict__ pt_idx,
+    const double* __restrict__ src, const double* __restrict__ dst, const int32_t* __restrict__ pt_idx,
     const int32_t* __restrict__ pt_off, int src_stride, const uint32_t* __restrict__ hyp,
     const int32_t* __restrict__ hyp_off, int hyp_off_len,
     int T, double thresh, double tq, double rate, int n_skip, double* __restrict__ out_params,
     uint8_t* __restrict__ out_inl, int32_t* __restrict__ out_nin, int32_t* __restrict__ out_best) {
-  for (int f = blockIdx.x; f < n_frames; f += gridDim.x) {
-    ransac_rigid_frame<LARGE, SCALE>(f, src, dst, pt_idx, pt_off, src_stride, hyp, hyp_off, hyp_off_len, T, thresh, tq,
-                                     rate, n_skip, out_params, out_inl, out_nin, out_best);
-    __syncthreads();  // the frame's LDS is free for the next one
-  }
+  ransac_rigid_frame<LARGE, SCALE>(blockIdx.x, src, dst, pt_idx, pt_off, src_stride, hyp, hyp_off, hyp_off_len, T, thresh,
+                                   tq, rate, n_skip, out_params, out_inl, out_nin, out_best);
 }
 
 }  // namespace
@@ -631,17 +456,13 @@ using namespace kcmc;
 
 template <bool SCALE>
 static int ransac_rigid_impl(kcmc_ctx* ctx, const double* src, const double* dst, const int32_t* pt_idx,
-                                 const int32_t* pt_off, int src_frame_stride, int n_frames, int max_n, int trials,
-                                 double thresh, double rate, int n_skip, double* out_params, uint8_t* out_inliers,
-                                 int32_t* out_n_inliers, int32_t* out_best_trial, int max_workgroups, kcmc_stream_t stream) {
+                             const int32_t* pt_off, int src_frame_stride, int n_frames, int max_n, int trials,
+                             double thresh, double rate, int n_skip, double* out_params, uint8_t* out_inliers,
+                             int32_t* out_n_inliers, int32_t* out_best_trial, kcmc_stream_t stream) {
   const char* const who = SCALE ? "kcmc_ransac_similarity: " : "kcmc_ransac_rigid: ";  // failures only
-  if (!ctx) return fail(KCMC_EINVAL, std::string(who) + "ctx is NULL");
-  if (n_frames < 0 || max_n < 0 || trials < 1) return fail(KCMC_EINVAL, std::string(who) + "bad sizes");
-  if (n_frames == 0) return KCMC_OK;
-  if (!pt_off || !out_params || !out_n_inliers || !out_best_trial || (max_n > 0 && (!src || !dst || !out_inliers)))
-    return fail(KCMC_EINVAL, std::string(who) + "NULL pointer");
-  if (max_n > kMaxN) return fail(KCMC_EUNSUPPORTED, std::string(who) + "max_n > 4096 points per frame");
-  if (pt_idx && src_frame_stride <= 0) return fail(KCMC_EINVAL, std::string(who) + "src_frame_stride must be > 0");
+  const int rc = check_ransac_args(who, ctx, src, dst, pt_idx, pt_off, src_frame_stride, n_frames, max_n, trials,
+                                   out_params, out_inliers, out_n_inliers, out_best_trial);
+  if (rc != KCMC_OK || n_frames == 0) return rc;
   const int need = max_n < 3 ? 3 : max_n;
   if (!ctx->hyp || ctx->hyp_trials != trials)
     return fail(KCMC_EINVAL, std::string(who) + "hypothesis tables not prepared for trials=" +
@@ -653,29 +474,18 @@ static int ransac_rigid_impl(kcmc_ctx* ctx, const double* src, const double* dst
                            wvals + (size_t)n_small + 16;
   const size_t lds_large = (size_t)need * (4 * sizeof(double) + 16) + (size_t)trials * (2 * sizeof(double) + sizeof(int)) +
                            (size_t)kMaxStack * kThreads * sizeof(double) + wvals + (size_t)need + 16;
-  const double tq = inlier_bound(thresh);
-  if ((max_n > 128 ? lds_large : lds_small) > 150 * 1024)
-    return fail(KCMC_EUNSUPPORTED, std::string(who) + "max_n/trials exceed the LDS budget");
-  hipStream_t s = (hipStream_t)stream;
-  const unsigned grid = (unsigned)(max_workgroups > 0 && max_workgroups < n_frames ? max_workgroups : n_frames);
-  hipLaunchKernelGGL((ransac_rigid_kernel<false, SCALE>), dim3(grid), dim3(kThreads), lds_small, s, n_frames, src, dst,
-                     pt_idx, pt_off, src_frame_stride, ctx->hyp, ctx->hyp_off, ctx->hyp_off_len, trials, thresh, tq, rate,
-                     n_skip, out_params, out_inliers, out_n_inliers, out_best_trial);
-  KCMC_TRY(launch_check("ransac_rigid_kernel<small>"));
-  if (max_n > 128) {
-    hipLaunchKernelGGL((ransac_rigid_kernel<true, SCALE>), dim3(grid), dim3(kThreads), lds_large, s, n_frames, src, dst,
-                       pt_idx, pt_off, src_frame_stride, ctx->hyp, ctx->hyp_off, ctx->hyp_off_len, trials, thresh, tq, rate,
-                       n_skip, out_params, out_inliers, out_n_inliers, out_best_trial);
-    KCMC_TRY(launch_check("ransac_rigid_kernel<large>"));
-  }
-  return KCMC_OK;
+  return launch_small_large(who, ransac_rigid_kernel<false, SCALE>, ransac_rigid_kernel<true, SCALE>, n_frames, max_n,
+                            lds_small, lds_large, (hipStream_t)stream, src, dst, pt_idx, pt_off, src_frame_stride,
+                            ctx->hyp, ctx->hyp_off, ctx->hyp_off_len, trials, thresh, inlier_bound(thresh), rate, n_skip,
+                            out_params, out_inliers, out_n_inliers, out_best_trial);
 }
 
 extern "C" int kcmc_ransac_rigid(kcmc_ctx* ctx, const double* src, const double* dst, const int32_t* pt_idx,
                                  const int32_t* pt_off, int src_frame_stride, int n_frames, int max_n, int trials,
                                  double thresh, double rate, int n_skip, double* out_params, uint8_t* out_inliers,
                                  int32_t* out_n_inliers, int32_t* out_best_trial, kcmc_stream_t stream) {
-  return ransac_rigid_impl<false>(ctx, src, dst, pt_idx, pt_off, src_frame_stride, n_frames, max_n, trials, thresh, rate, n_skip, out_params, out_inliers, out_n_inliers, out_best_trial, 0, stream);
+  return ransac_rigid_impl<false>(ctx, src, dst, pt_idx, pt_off, src_frame_stride, n_frames, max_n, trials, thresh, rate,
+                                  n_skip, out_params, out_inliers, out_n_inliers, out_best_trial, stream);
 }
 
 extern "C" int kcmc_ransac_similarity(kcmc_ctx* ctx, const double* src, const double* dst, const int32_t* pt_idx,
@@ -683,5 +493,5 @@ extern "C" int kcmc_ransac_similarity(kcmc_ctx* ctx, const double* src, const do
                                       double thresh, double rate, int n_skip, double* out_params, uint8_t* out_inliers,
                                       int32_t* out_n_inliers, int32_t* out_best_trial, kcmc_stream_t stream) {
   return ransac_rigid_impl<true>(ctx, src, dst, pt_idx, pt_off, src_frame_stride, n_frames, max_n, trials, thresh, rate,
-                                 n_skip, out_params, out_inliers, out_n_inliers, out_best_trial, 0, stream);
+                                 n_skip, out_params, out_inliers, out_n_inliers, out_best_trial, stream);
 }

@@ -1,6 +1,7 @@
 // Model-independent pieces of the batched RANSAC kernels (ransac.hip: rigid,
 // ransac_model.hip: affine / projective): launch shape, numpy's pairwise-summation
-// split plan, skimage's selection order and workgroup / wave sums.
+// split plan, skimage's selection order, workgroup / wave sums, the control skeleton of a
+// scoring workgroup and the launchers' argument checks and small / large launch pair.
 #pragma once
 
 #include <climits>
@@ -360,6 +361,265 @@ __device__ inline double block_sum(double v, double* red) {
 __device__ __forceinline__ double wave_sum(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
+}
+
+// ---------------------------------------------------------------- the scoring skeleton
+// What a scoring workgroup does around its model's fit, residual and phase-A scorer, the same
+// for every model: which frames it owns, the point gather, the workgroup reductions, numpy's
+// pairwise sum by one thread, the walk over a wave's candidate trials and skimage's selection.
+// A model's own part comes in as a functor; nothing here knows which model calls it.
+
+// The workgroup's small static scratch for the reductions below.  (The selection's flag
+// s_any_zero stays a variable of its own: the compiler packs it into the padding behind the
+// Plan, inside this struct it would cost the large kernels 16 bytes.)
+struct Scratch {
+  double min[kThreads / 64];
+  double bestS[kThreads / 64];
+  int cnt[kThreads / 64];
+  int best[kThreads / 64 * 2];  // (count, trial) per wave; then the selection's (best_t, best_c)
+};
+
+// Frame f's points [p0, p0 + N) and the start of N's hypothesis table.  A frame RANSAC does not
+// run on (fewer than n_skip or min_n points, more than kMaxN, or no table for N) gets NaN
+// parameters (NPARAM per frame), an empty mask and best_trial -1 from the small launch.
+// false: this launch has nothing more to do for the frame.
+template <bool LARGE, int NPARAM>
+__device__ __forceinline__ bool frame_begin(int f, const int32_t* __restrict__ pt_off, int n_skip, int min_n,
+                                            const int32_t* __restrict__ hyp_off, int hyp_off_len,
+                                            double* __restrict__ out_params, uint8_t* __restrict__ out_inl,
+                                            int32_t* __restrict__ out_nin, int32_t* __restrict__ out_best, int& p0,
+                                            int& N, int& hoff) {
+  const int tid = threadIdx.x;
+  p0 = pt_off[f];
+  N = pt_off[f + 1] - p0;
+  const bool skip_frame = N < n_skip || N < min_n || N > kMaxN;
+  hoff = (!skip_frame && N < hyp_off_len) ? hyp_off[N] : -1;
+  const bool nan_frame = skip_frame || hoff < 0;
+  if (LARGE != (!nan_frame && N > 128)) return false;  // the other launch owns this frame
+  if (nan_frame) {
+    if (tid < NPARAM) out_params[NPARAM * (size_t)f + tid] = NAN;
+    for (int k = tid; k < N; k += kThreads) out_inl[p0 + k] = 0;
+    if (tid == 0) {
+      out_nin[f] = skip_frame ? 0 : -1;  // -1: no hypothesis table was prepared for N
+      out_best[f] = -1;
+    }
+    return false;
+  }
+  return true;
+}
+
+// Point p of frame f: (x, y) from src, (u, v) from dst, through the index list pt_idx
+// (src[f * src_stride + q], dst[q] with q = pt_idx[p]) or contiguous (both at p).
+__device__ __forceinline__ void gather_point(const double* __restrict__ src, const double* __restrict__ dst,
+                                             const int32_t* __restrict__ pt_idx, int src_stride, int f, int p,
+                                             double& x, double& y, double& u, double& v) {
+  size_t si, di;
+  if (pt_idx) {
+    const int q = pt_idx[p];
+    si = (size_t)f * src_stride + q;
+    di = (size_t)q;
+  } else {
+    si = di = (size_t)p;
+  }
+  x = src[2 * si];
+  y = src[2 * si + 1];
+  u = dst[2 * di];
+  v = dst[2 * di + 1];
+}
+
+// Workgroup maximum of a count (>= -1) and OR of a 0 / 1 flag, in every thread.  One barrier;
+// a caller that uses s_cnt again puts a barrier after it.
+__device__ __forceinline__ void block_max_flag(int& m, int& flag, int* s_cnt) {
+  for (int o = 32; o > 0; o >>= 1) {
+    m = max(m, __shfl_xor(m, o));
+    flag |= __shfl_xor(flag, o);
+  }
+  if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = (m + 1) | (flag << 30);  // counts <= kMaxN
+  __syncthreads();
+#pragma unroll
+  for (int w = 0; w < kThreads / 64; ++w) {
+    const int v = s_cnt[w];
+    flag |= v >> 30;
+    m = max(m, (v & 0x3fffffff) - 1);
+  }
+}
+
+// Workgroup minimum in every thread (one barrier).
+__device__ __forceinline__ double block_min(double v, double* s_min) {
+  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o));
+  if ((threadIdx.x & 63) == 0) s_min[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return fmin(fmin(s_min[0], s_min[1]), fmin(s_min[2], s_min[3]));
+}
+
+// numpy pairwise_sum over r2(start + k), k < n, for n <= 128 by one thread:
+// n < 8 sequential, else 8 strided accumulators + sequential remainder.
+template <class R2>
+__device__ __forceinline__ double pw_leaf(R2 r2, int start, int n) {
+  if (n < 8) {
+    double res = 0.0;
+    for (int i = 0; i < n; ++i) res += r2(start + i);
+    return res;
+  }
+  double r[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) r[j] = r2(start + j);
+  int i = 8;
+  const int nfull = n - (n % 8);
+  for (; i < nfull; i += 8) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r[j] += r2(start + i + j);
+  }
+  double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+  for (; i < n; ++i) res += r2(start + i);
+  return res;
+}
+
+// The exact S of one trial by one thread, wave_pairwise's counterpart: a single leaf for
+// N <= 128 (fully in registers), else numpy's split plan with the thread's combine stack in
+// LDS (stk[level * kThreads + tid]).
+template <bool LARGE, class R2>
+__device__ __forceinline__ double thread_pairwise(R2 r2, int N, const Plan& plan, double* stk, int tid) {
+  if (!LARGE) return pw_leaf(r2, 0, N);
+  int sp = 0;
+  for (int l = 0; l < plan.n; ++l) {
+    stk[sp++ * kThreads + tid] = pw_leaf(r2, plan.start[l], plan.len[l]);
+    for (int c = plan.pops[l]; c > 0; --c) {
+      const double b = stk[--sp * kThreads + tid];
+      const double a = stk[(sp - 1) * kThreads + tid];
+      stk[(sp - 1) * kThreads + tid] = a + b;
+    }
+  }
+  return stk[tid];
+}
+
+// A thread's running best of skimage's selection order.
+struct Best {
+  int c = -1;
+  double S = INFINITY;
+  int t = INT_MAX;
+  __device__ __forceinline__ void take(int oc, double oS, int ot) {
+    if (better(oc, oS, ot, c, S, t)) {
+      c = oc;
+      S = oS;
+      t = ot;
+    }
+  }
+};
+
+// Exact scoring of every trial, each by one thread (the frames phase A cannot decide):
+// score(t, cnt) returns numpy's S of trial t and adds its inliers to cnt, NaN for a trial
+// without a model.  Skipped trials (estimate() False) and NaN scores never win; with 0 inliers
+// a trial wins only with S < inf (skimage's strict comparisons against (0, inf)).
+template <class Score>
+__device__ __forceinline__ void exact_trials(int T, Score score, double* tS, int* tC, Best& best, bool& any_zero) {
+  for (int t = threadIdx.x; t < T; t += kThreads) {
+    int cnt = 0;
+    const double S = score(t, cnt);
+    tS[t] = S;
+    tC[t] = cnt;
+    if (!isnan(S) && (cnt > 0 || S < INFINITY)) {
+      if (S <= 0.0) any_zero = true;
+      best.take(cnt, S, t);
+    }
+  }
+}
+
+// This wave's candidate trials (t = t0 + lane, pred(t) in its lane), one after the other with
+// the whole wave in body(t): t is wave-uniform there.
+template <class Pred, class Body>
+__device__ __forceinline__ void for_each_wave_trial(int T, Pred pred, Body body) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int t0 = wave * 64; t0 < T; t0 += kThreads) {
+    const int t = t0 + lane;
+    uint64_t todo = __ballot(t < T && pred(t));
+    while (todo) {
+      const int tc = t0 + __builtin_ctzll(todo);
+      todo &= todo - 1;
+      body(tc);
+    }
+  }
+}
+
+// The selection's tail: workgroup argmax of (count, -S, -t) over every thread's best, and,
+// when an exactly scored trial had S <= 0, skimage's early exit from the trials' records
+// tS / tC (s_any_zero: zero before the barrier that precedes the scoring).  best_t = -1 and
+// best_c = 0: no trial can be selected.
+__device__ __forceinline__ void select_best(Best b, bool any_zero, int T, const double* tS, const int* tC, Scratch& sc,
+                                            int& s_any_zero, int& best_t, int& best_c) {
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  for (int o = 32; o > 0; o >>= 1) b.take(__shfl_xor(b.c, o), __shfl_xor(b.S, o), __shfl_xor(b.t, o));
+  if (lane == 0) {
+    sc.best[2 * wave] = b.c;
+    sc.best[2 * wave + 1] = b.t;
+    sc.bestS[wave] = b.S;
+  }
+  if (any_zero) atomicOr(&s_any_zero, 1);
+  __syncthreads();
+  if (tid == 0) {
+    Best fin;
+    for (int w = 0; w < kThreads / 64; ++w) fin.take(sc.best[2 * w], sc.bestS[w], sc.best[2 * w + 1]);
+    if (s_any_zero) {
+      // skimage stops as soon as the running best has S <= 0 (fit.py:862-869):
+      // replay the trial sequence to find where it stopped.
+      int c0 = 0, t0 = -1;
+      double S0 = INFINITY;
+      for (int t = 0; t < T; ++t) {
+        const double S = tS[t];
+        const int c = tC[t];
+        if (isnan(S)) continue;
+        if (c > c0 || (c == c0 && S < S0)) {
+          c0 = c;
+          S0 = S;
+          t0 = t;
+          if (S0 <= 0.0) break;
+        }
+      }
+      fin.t = t0 < 0 ? INT_MAX : t0;
+      fin.c = c0;
+    }
+    // only this thread has read sc.best since the barrier
+    sc.best[0] = (fin.t == INT_MAX) ? -1 : fin.t;
+    sc.best[1] = (fin.t == INT_MAX) ? 0 : fin.c;
+  }
+  __syncthreads();
+  best_t = sc.best[0];
+  best_c = sc.best[1];
+}
+
+// ---------------------------------------------------------------- host side of the launchers
+// The argument checks every RANSAC entry point makes (who = "kcmc_ransac_...: ", the entry
+// that was called).  KCMC_OK with n_frames == 0: nothing to launch.
+inline int check_ransac_args(const char* who, const kcmc_ctx* ctx, const double* src, const double* dst,
+                             const int32_t* pt_idx, const int32_t* pt_off, int src_frame_stride, int n_frames,
+                             int max_n, int trials, const double* out_params, const uint8_t* out_inliers,
+                             const int32_t* out_n_inliers, const int32_t* out_best_trial) {
+  if (!ctx) return fail(KCMC_EINVAL, std::string(who) + "ctx is NULL");
+  if (n_frames < 0 || max_n < 0 || trials < 1) return fail(KCMC_EINVAL, std::string(who) + "bad sizes");
+  if (n_frames == 0) return KCMC_OK;
+  if (!pt_off || !out_params || !out_n_inliers || !out_best_trial || (max_n > 0 && (!src || !dst || !out_inliers)))
+    return fail(KCMC_EINVAL, std::string(who) + "NULL pointer");
+  if (max_n > kMaxN) return fail(KCMC_EUNSUPPORTED, std::string(who) + "max_n > 4096 points per frame");
+  if (pt_idx && src_frame_stride <= 0) return fail(KCMC_EINVAL, std::string(who) + "src_frame_stride must be > 0");
+  return KCMC_OK;
+}
+
+// One workgroup per frame: the small kernel (frames with N <= 128 and the NaN frames) and, when
+// a frame can have more points, the large one (narrower grids measured slower beside the warp,
+// DESIGN 6d).
+template <class... P, class... A>
+inline int launch_small_large(const char* who, void (*small)(P...), void (*large)(P...), int n_frames, int max_n,
+                              size_t lds_small, size_t lds_large, hipStream_t s, A... args) {
+  if ((max_n > 128 ? lds_large : lds_small) > 150 * 1024)
+    return fail(KCMC_EUNSUPPORTED, std::string(who) + "max_n/trials exceed the LDS budget");
+  hipLaunchKernelGGL(small, dim3((unsigned)n_frames), dim3(kThreads), lds_small, s, args...);
+  KCMC_TRY(launch_check((std::string(who) + "small scoring kernel").c_str()));
+  if (max_n > 128) {
+    hipLaunchKernelGGL(large, dim3((unsigned)n_frames), dim3(kThreads), lds_large, s, args...);
+    KCMC_TRY(launch_check((std::string(who) + "large scoring kernel").c_str()));
+  }
+  return KCMC_OK;
 }
 
 }  // namespace ransac_common

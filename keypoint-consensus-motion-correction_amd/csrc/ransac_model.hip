@@ -352,28 +352,6 @@ __device__ __forceinline__ double resid2(const double (&h)[9], const Pts& P, int
   return r * r;
 }
 
-template <int MODEL>
-__device__ __forceinline__ double pw_leaf(const double (&h)[9], const Pts& P, int start, int n, double thresh,
-                                          int& cnt) {
-  if (n < 8) {
-    double res = 0.0;
-    for (int i = 0; i < n; ++i) res += resid2<MODEL>(h, P, start + i, thresh, cnt);
-    return res;
-  }
-  double r[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = resid2<MODEL>(h, P, start + j, thresh, cnt);
-  int i = 8;
-  const int nfull = n - (n % 8);
-  for (; i < nfull; i += 8) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] += resid2<MODEL>(h, P, start + i + j, thresh, cnt);
-  }
-  double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-  for (; i < n; ++i) res += resid2<MODEL>(h, P, start + i, thresh, cnt);
-  return res;
-}
-
 // Phase A of the scoring (the rigid kernel's, ransac.hip): the exact inlier count through
 // q < tq (q computed as resid2 computes it) and the estimate Sd = sum q_k, summed in
 // sequence in fp64 (round 6; was an fp32 sum of (float)q_k): within sd_eps(N) of numpy's S,
@@ -463,23 +441,6 @@ __device__ __forceinline__ HModel fit_trial(const Pts& P, uint64_t pr) {
   }
 }
 
-__device__ __forceinline__ void gather_point(const double* __restrict__ src, const double* __restrict__ dst,
-                                             const int32_t* __restrict__ pt_idx, int src_stride, int f, int p,
-                                             double& x, double& y, double& u, double& v) {
-  size_t si, di;
-  if (pt_idx) {
-    const int q = pt_idx[p];
-    si = (size_t)f * src_stride + q;
-    di = (size_t)q;
-  } else {
-    si = di = (size_t)p;
-  }
-  x = src[2 * si];
-  y = src[2 * si + 1];
-  u = dst[2 * di];
-  v = dst[2 * di + 1];
-}
-
 // The scoring kernel ends each frame with its refit for the homography (kFusedRefit); the
 // affine model runs ransac_model_refit_kernel after the scoring.
 template <int MODEL>
@@ -501,33 +462,16 @@ __device__ __forceinline__ void ransac_model_score_frame(
     double* out_params, uint8_t* __restrict__ out_inl, int32_t* __restrict__ out_nin, int32_t* __restrict__ out_best) {
   constexpr int K = MODEL == KCMC_MODEL_AFFINE ? 3 : 4;
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  __shared__ int s_cnt[kThreads / 64];
-  __shared__ double s_min[kThreads / 64];
-  __shared__ int s_best[kThreads / 64 * 2];
-  __shared__ double s_bestS[kThreads / 64];
+  __shared__ Scratch sc;
   __shared__ int s_any_zero;
-  __shared__ int s_final_t;
-  __shared__ int s_final_c;
   __shared__ Plan s_plan;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
-  const int p0 = pt_off[f];
-  const int N = pt_off[f + 1] - p0;
-
-  const bool skip_frame = N < n_skip || N <= K || N > kMaxN;
-  const int hoff = (!skip_frame && N < hyp_off_len) ? hyp_off[N] : -1;
-  const bool nan_frame = skip_frame || hoff < 0;
-  if (LARGE != (!nan_frame && N > 128)) return;  // the other launch owns this frame
-  if (nan_frame) {
-    if (tid < 9) out_params[9 * (size_t)f + tid] = NAN;
-    for (int k = tid; k < N; k += kThreads) out_inl[p0 + k] = 0;
-    if (tid == 0) {
-      out_nin[f] = skip_frame ? 0 : -1;  // -1: no hypothesis table was prepared for N
-      out_best[f] = -1;
-    }
+  int p0, N, hoff;
+  if (!frame_begin<LARGE, 9>(f, pt_off, n_skip, K + 1, hyp_off, hyp_off_len, out_params, out_inl, out_nin, out_best, p0,
+                             N, hoff))
     return;
-  }
 
   // LDS: sx, sy, dx, dy [N] f64 | trial S [T] f64 | [LARGE: stack [kMaxStack][256] f64]
   //      | per-wave leaf values [4][128] f64 | trial count [T] i32 | the winner's inlier mask [N] u8
@@ -597,140 +541,45 @@ __device__ __forceinline__ void ransac_model_score_frame(
       }
     }
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    mcount = max(mcount, __shfl_xor(mcount, o));
-    flag |= __shfl_xor(flag, o);
-  }
-  if (lane == 0) s_cnt[wave] = (mcount + 1) | (flag << 30);  // counts <= kMaxN
-  __syncthreads();
-#pragma unroll
-  for (int w = 0; w < kThreads / 64; ++w) {
-    const int v = s_cnt[w];
-    flag |= v >> 30;
-    mcount = max(mcount, (v & 0x3fffffff) - 1);
-  }
+  block_max_flag(mcount, flag, sc.cnt);
   const bool exact = flag != 0 || mcount <= 0;
 
-  int bc = -1, bt = INT_MAX;
-  double bS = INFINITY;
+  Best best;
   bool any_zero = false;
   if (exact) {
-    for (int t = tid; t < T; t += kThreads) {
-      const HModel m = fit_trial<MODEL>(P, H[t]);
-      int cnt = 0;
-      double S = NAN;
-      if (m.ok) {
-        if (!LARGE) {
-          S = pw_leaf<MODEL>(m.h, P, 0, N, thresh, cnt);
-        } else {
-          int sp = 0;
-          for (int l = 0; l < s_plan.n; ++l) {
-            stk[sp++ * kThreads + tid] = pw_leaf<MODEL>(m.h, P, s_plan.start[l], s_plan.len[l], thresh, cnt);
-            for (int c = s_plan.pops[l]; c > 0; --c) {
-              const double b = stk[--sp * kThreads + tid];
-              const double a = stk[(sp - 1) * kThreads + tid];
-              stk[(sp - 1) * kThreads + tid] = a + b;
-            }
-          }
-          S = stk[tid];
-        }
-      }
-      tS[t] = S;
-      tC[t] = cnt;
-      // skipped trials (estimate() False) and NaN scores never win; with 0 inliers a
-      // trial wins only with S < inf (skimage's strict comparisons against (0, inf))
-      const bool valid = m.ok && !isnan(S) && (cnt > 0 || S < INFINITY);
-      if (valid) {
-        if (S <= 0.0) any_zero = true;
-        if (better(cnt, S, t, bc, bS, bt)) {
-          bc = cnt;
-          bS = S;
-          bt = t;
-        }
-      }
-    }
+    exact_trials(
+        T,
+        [&](int t, int& cnt) {
+          const HModel m = fit_trial<MODEL>(P, H[t]);
+          if (!m.ok) return (double)NAN;
+          return thread_pairwise<LARGE>([&](int k) { return resid2<MODEL>(m.h, P, k, thresh, cnt); }, N, s_plan, stk,
+                                        tid);
+        },
+        tS, tC, best, any_zero);
   } else {
     const double eps = sd_eps(N);
     double lm = INFINITY;
     for (int t = tid; t < T; t += kThreads)
       if (tC[t] == mcount) lm = fmin(lm, tS[t] * (1.0 + eps));
-    for (int o = 32; o > 0; o >>= 1) lm = fmin(lm, __shfl_xor(lm, o));
-    if (lane == 0) s_min[wave] = lm;
-    __syncthreads();
-    const double minhi = fmin(fmin(s_min[0], s_min[1]), fmin(s_min[2], s_min[3]));
+    const double minhi = block_min(lm, sc.min);
     double* vals = wvals + wave * 128;
     double* wstk = stk + wave * kMaxStack;  // LARGE: the wave's combine stack
-    for (int t0 = wave * 64; t0 < T; t0 += kThreads) {
-      const int t = t0 + lane;
-      uint64_t cand = __ballot(t < T && tC[t] == mcount && tS[t] * (1.0 - eps) <= minhi);
-      while (cand) {
-        const int tc = t0 + __builtin_ctzll(cand);
-        cand &= cand - 1;
-        const HModel m = fit_trial<MODEL>(P, H[tc]);  // ok: it has a count
-        const double S = wave_pairwise<LARGE>(
-            [&](int k) {
-              int c = 0;
-              return resid2<MODEL>(m.h, P, k, thresh, c);
-            },
-            N, s_plan, vals, wstk, lane);
-        if (!isnan(S) && better(mcount, S, tc, bc, bS, bt)) {  // wave-uniform
-          bc = mcount;
-          bS = S;
-          bt = tc;
-        }
-      }
-    }
+    // phase B: this wave's candidate trials, each scored by the whole wave
+    for_each_wave_trial(
+        T, [&](int t) { return tC[t] == mcount && tS[t] * (1.0 - eps) <= minhi; },
+        [&](int tc) {
+          const HModel m = fit_trial<MODEL>(P, H[tc]);  // ok: it has a count
+          const double S = wave_pairwise<LARGE>(
+              [&](int k) {
+                int c = 0;
+                return resid2<MODEL>(m.h, P, k, thresh, c);
+              },
+              N, s_plan, vals, wstk, lane);
+          if (!isnan(S)) best.take(mcount, S, tc);  // wave-uniform
+        });
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    const int oc = __shfl_xor(bc, o);
-    const double oS = __shfl_xor(bS, o);
-    const int ot = __shfl_xor(bt, o);
-    if (better(oc, oS, ot, bc, bS, bt)) {
-      bc = oc;
-      bS = oS;
-      bt = ot;
-    }
-  }
-  if (lane == 0) {
-    s_best[2 * wave] = bc;
-    s_best[2 * wave + 1] = bt;
-    s_bestS[wave] = bS;
-  }
-  if (any_zero) atomicOr(&s_any_zero, 1);
-  __syncthreads();
-  if (tid == 0) {
-    int fc = -1, ft = INT_MAX;
-    double fS = INFINITY;
-    for (int w = 0; w < kThreads / 64; ++w)
-      if (better(s_best[2 * w], s_bestS[w], s_best[2 * w + 1], fc, fS, ft)) {
-        fc = s_best[2 * w];
-        fS = s_bestS[w];
-        ft = s_best[2 * w + 1];
-      }
-    if (s_any_zero) {
-      // skimage stops as soon as the running best has S <= 0 (fit.py:862-869)
-      int c0 = 0, t0 = -1;
-      double S0 = INFINITY;
-      for (int t = 0; t < T; ++t) {
-        const double S = tS[t];
-        const int c = tC[t];
-        if (isnan(S)) continue;
-        if (c > c0 || (c == c0 && S < S0)) {
-          c0 = c;
-          S0 = S;
-          t0 = t;
-          if (S0 <= 0.0) break;
-        }
-      }
-      ft = t0 < 0 ? INT_MAX : t0;
-      fc = c0;
-    }
-    s_final_t = (ft == INT_MAX) ? -1 : ft;
-    s_final_c = (ft == INT_MAX) ? 0 : fc;
-  }
-  __syncthreads();
-  const int best_t = s_final_t;
-  const int best_c = s_final_c;
+  int best_t, best_c;
+  select_best(best, any_zero, T, tS, tC, sc, s_any_zero, best_t, best_c);
 
   HModel bm;
   bm.ok = false;
@@ -1005,21 +854,18 @@ __device__ __forceinline__ void qr_rows(int N, int lane, PointFn point, InlierFn
   }
 }
 
-// Workgroup g scores frames g, g + grid, ... (the product launches one per frame).
+// One workgroup per frame.
 // (projective: 2 waves per SIMD, its scoring alone needs 231 VGPRs)
 template <int MODEL, bool LARGE>
 __global__ __launch_bounds__(kThreads, MODEL == KCMC_MODEL_AFFINE ? 1 : 2) void
 ransac_model_score_kernel(
-    int n_frames, const double* __restrict__ src, const double* __restrict__ dst, const int32_t* __restrict__ pt_idx,
+    const double* __restrict__ src, const double* __restrict__ dst, const int32_t* __restrict__ pt_idx,
     const int32_t* __restrict__ pt_off, int src_stride, const uint64_t* __restrict__ hyp,
     const int32_t* __restrict__ hyp_off, int hyp_off_len, int T, double thresh, double tq, int n_skip, double rate,
     double* out_params, uint8_t* __restrict__ out_inl, int32_t* __restrict__ out_nin,
     int32_t* __restrict__ out_best) {
-  for (int f = blockIdx.x; f < n_frames; f += gridDim.x) {
-    ransac_model_score_frame<MODEL, LARGE>(f, src, dst, pt_idx, pt_off, src_stride, hyp, hyp_off, hyp_off_len, T,
-                                           thresh, tq, n_skip, rate, out_params, out_inl, out_nin, out_best);
-    __syncthreads();  // the frame's LDS is free for the next one
-  }
+  ransac_model_score_frame<MODEL, LARGE>(blockIdx.x, src, dst, pt_idx, pt_off, src_stride, hyp, hyp_off, hyp_off_len, T,
+                                         thresh, tq, n_skip, rate, out_params, out_inl, out_nin, out_best);
 }
 
 // The affine model's refit after the scoring: one wave per frame, the points through pt_idx
@@ -1146,22 +992,19 @@ __device__ __forceinline__ void refit_frame(int N, int lane, PointFn point, Inli
 
 using namespace kcmc;
 
-static int ransac_model_impl(kcmc_ctx* ctx, int model, const double* src, const double* dst,
+extern "C" int kcmc_ransac_model(kcmc_ctx* ctx, int model, const double* src, const double* dst,
                                  const int32_t* pt_idx, const int32_t* pt_off, int src_frame_stride, int n_frames,
                                  int max_n, int trials, double thresh, double rate, int n_skip, double* out_params,
                                  uint8_t* out_inliers, int32_t* out_n_inliers, int32_t* out_best_trial,
-                                 int max_workgroups, kcmc_stream_t stream) {
-  if (!ctx) return fail(KCMC_EINVAL, "kcmc_ransac_model: ctx is NULL");
+                                 kcmc_stream_t stream) {
+  const char* const who = "kcmc_ransac_model: ";
   if (model != KCMC_MODEL_AFFINE && model != KCMC_MODEL_PROJECTIVE)
     return fail(KCMC_EINVAL, "kcmc_ransac_model: model must be KCMC_MODEL_AFFINE or KCMC_MODEL_PROJECTIVE "
                              "(the Euclidean model is kcmc_ransac_rigid)");
-  if (n_frames < 0 || max_n < 0 || trials < 1) return fail(KCMC_EINVAL, "kcmc_ransac_model: bad sizes");
   if (!(rate > 0.0)) return fail(KCMC_EINVAL, "kcmc_ransac_model: spatial_rate must be > 0");
-  if (n_frames == 0) return KCMC_OK;
-  if (!pt_off || !out_params || !out_n_inliers || !out_best_trial || (max_n > 0 && (!src || !dst || !out_inliers)))
-    return fail(KCMC_EINVAL, "kcmc_ransac_model: NULL pointer");
-  if (max_n > kMaxN) return fail(KCMC_EUNSUPPORTED, "kcmc_ransac_model: max_n > 4096 points per frame");
-  if (pt_idx && src_frame_stride <= 0) return fail(KCMC_EINVAL, "kcmc_ransac_model: src_frame_stride must be > 0");
+  const int rc = check_ransac_args(who, ctx, src, dst, pt_idx, pt_off, src_frame_stride, n_frames, max_n, trials,
+                                   out_params, out_inliers, out_n_inliers, out_best_trial);
+  if (rc != KCMC_OK || n_frames == 0) return rc;
   const int ms = model == KCMC_MODEL_AFFINE ? 3 : 4;
   const HypTables& tab = ctx->mhyp[ms];
   if (!tab.dev || tab.trials != trials)
@@ -1176,42 +1019,22 @@ static int ransac_model_impl(kcmc_ctx* ctx, int model, const double* src, const 
                            (size_t)trials * (sizeof(double) + sizeof(int)) + wvals + 16 + (((size_t)n_small + 15) & ~15);
   const size_t lds_large = (size_t)need * 4 * sizeof(double) + (size_t)trials * (sizeof(double) + sizeof(int)) + wvals +
                            (size_t)kMaxStack * kThreads * sizeof(double) + 16 + (((size_t)need + 15) & ~15);
-  if ((max_n > 128 ? lds_large : lds_small) > 150 * 1024)
-    return fail(KCMC_EUNSUPPORTED, "kcmc_ransac_model: max_n/trials exceed the LDS budget");
-  const double tq = inlier_bound(thresh);
   hipStream_t s = (hipStream_t)stream;
   // The scoring kernel writes out_params: the homography's refit is fused into it (one wave
   // per frame, points and mask from LDS); the affine model's hypothesis model goes there
-  // first and ransac_model_refit_kernel overwrites it with the refit.  No workspace: a stream-ordered pool allocation cost
-  // ~0.2 ms of host time per call.
-  const unsigned grid = (unsigned)(max_workgroups > 0 && max_workgroups < n_frames ? max_workgroups : n_frames);
-  if (model == KCMC_MODEL_AFFINE) {
-    hipLaunchKernelGGL((ransac_model_score_kernel<KCMC_MODEL_AFFINE, false>), dim3(grid), dim3(kThreads),
-                       lds_small, s, n_frames, src, dst, pt_idx, pt_off, src_frame_stride, tab.dev, tab.off, tab.off_len,
-                       trials, thresh, tq, n_skip, rate, out_params, out_inliers, out_n_inliers, out_best_trial);
-    if (max_n > 128)
-      hipLaunchKernelGGL((ransac_model_score_kernel<KCMC_MODEL_AFFINE, true>), dim3(grid), dim3(kThreads),
-                         lds_large, s, n_frames, src, dst, pt_idx, pt_off, src_frame_stride, tab.dev, tab.off, tab.off_len,
-                         trials, thresh, tq, n_skip, rate, out_params, out_inliers, out_n_inliers, out_best_trial);
-    hipLaunchKernelGGL((ransac_model_refit_kernel<KCMC_MODEL_AFFINE>), dim3((unsigned)ceil_div(n_frames, 4)), dim3(256),
-                       0, s, src, dst, pt_idx, pt_off, src_frame_stride, out_inliers, out_n_inliers, n_frames, rate,
-                       out_params);
-  } else {
-    hipLaunchKernelGGL((ransac_model_score_kernel<KCMC_MODEL_PROJECTIVE, false>), dim3(grid), dim3(kThreads),
-                       lds_small, s, n_frames, src, dst, pt_idx, pt_off, src_frame_stride, tab.dev, tab.off, tab.off_len,
-                       trials, thresh, tq, n_skip, rate, out_params, out_inliers, out_n_inliers, out_best_trial);
-    if (max_n > 128)
-      hipLaunchKernelGGL((ransac_model_score_kernel<KCMC_MODEL_PROJECTIVE, true>), dim3(grid), dim3(kThreads),
-                         lds_large, s, n_frames, src, dst, pt_idx, pt_off, src_frame_stride, tab.dev, tab.off, tab.off_len,
-                         trials, thresh, tq, n_skip, rate, out_params, out_inliers, out_n_inliers, out_best_trial);
-  }
-  return launch_check("ransac_model kernels");
-}
-
-extern "C" int kcmc_ransac_model(kcmc_ctx* ctx, int model, const double* src, const double* dst,
-                                 const int32_t* pt_idx, const int32_t* pt_off, int src_frame_stride, int n_frames,
-                                 int max_n, int trials, double thresh, double rate, int n_skip, double* out_params,
-                                 uint8_t* out_inliers, int32_t* out_n_inliers, int32_t* out_best_trial,
-                                 kcmc_stream_t stream) {
-  return ransac_model_impl(ctx, model, src, dst, pt_idx, pt_off, src_frame_stride, n_frames, max_n, trials, thresh, rate, n_skip, out_params, out_inliers, out_n_inliers, out_best_trial, 0, stream);
+  // first and ransac_model_refit_kernel overwrites it with the refit.  No workspace: a
+  // stream-ordered pool allocation cost ~0.2 ms of host time per call.
+  auto score = [&](auto small, auto large) {
+    return launch_small_large(who, small, large, n_frames, max_n, lds_small, lds_large, s, src, dst, pt_idx, pt_off,
+                              src_frame_stride, tab.dev, tab.off, tab.off_len, trials, thresh, inlier_bound(thresh),
+                              n_skip, rate, out_params, out_inliers, out_n_inliers, out_best_trial);
+  };
+  if (model == KCMC_MODEL_PROJECTIVE)
+    return score(ransac_model_score_kernel<KCMC_MODEL_PROJECTIVE, false>,
+                 ransac_model_score_kernel<KCMC_MODEL_PROJECTIVE, true>);
+  KCMC_TRY(score(ransac_model_score_kernel<KCMC_MODEL_AFFINE, false>, ransac_model_score_kernel<KCMC_MODEL_AFFINE, true>));
+  hipLaunchKernelGGL((ransac_model_refit_kernel<KCMC_MODEL_AFFINE>), dim3((unsigned)ceil_div(n_frames, 4)), dim3(256),
+                     0, s, src, dst, pt_idx, pt_off, src_frame_stride, out_inliers, out_n_inliers, n_frames, rate,
+                     out_params);
+  return launch_check("ransac_model_refit_kernel");
 }

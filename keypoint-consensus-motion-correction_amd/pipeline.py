@@ -17,6 +17,7 @@ from typing import Callable, List, Optional, Tuple
 import numpy as np
 import torch
 
+from . import _lib
 from . import affines as _aff
 from . import stages
 
@@ -199,8 +200,7 @@ def prepare_ransac(device, cfg: AlignConfig) -> None:
 def _check_point_counts(cons: stages.Consensus, cfg: AlignConfig) -> None:
     """skimage raises when a frame is not skipped but has N <= min_samples (fit.py:798-799);
     only reachable when N_KP_FRAME_SKIP <= min_samples (the host then reads pt_off)."""
-    ms = {"euclidean": cfg.ransac_min_samples, "similarity": cfg.ransac_min_samples, "affine": 3,
-          "projective": 4}[cfg.ransac_model]
+    ms = _lib.MODEL_MIN_SAMPLES[cfg.ransac_model]
     skip = cfg.effective_frame_skip
     if skip > ms:
         return
@@ -237,21 +237,9 @@ def ransac_stage(match: stages.MatchResult, kp_tpl: torch.Tensor, cons: stages.C
                                  n_skip=cfg.effective_frame_skip, stream=stream)
     else:
         pt_off, pt_idx = lists_dev if lists_dev is not None else consensus_to_device(cons, dev)
-        if cfg.ransac_model == "euclidean":
-            return stages.ransac_rigid(src, kp_tpl, pt_off, cons.pt_off, pt_idx=pt_idx,
-                                       src_frame_stride=n_tpl, trials=cfg.ransac_trials,
-                                       residual_threshold=cfg.ransac_threshold, spatial_rate=cfg.spatial_rate,
-                                       n_skip=cfg.n_kp_frame_skip, seed=cfg.seed, min_samples=cfg.ransac_min_samples)
-        if cfg.ransac_model == "similarity":
-            return stages.ransac_similarity(src, kp_tpl, pt_off, cons.pt_off, pt_idx=pt_idx,
-                                            src_frame_stride=n_tpl, trials=cfg.ransac_trials,
-                                            residual_threshold=cfg.ransac_threshold, spatial_rate=cfg.spatial_rate,
-                                            n_skip=cfg.effective_frame_skip, seed=cfg.seed,
-                                            min_samples=cfg.ransac_min_samples)
-        rr = stages.ransac_model(src, kp_tpl, pt_off, cons.pt_off, model=cfg.ransac_model,
-                                 pt_idx=pt_idx, src_frame_stride=n_tpl, trials=cfg.ransac_trials,
-                                 residual_threshold=cfg.ransac_threshold, spatial_rate=cfg.spatial_rate,
-                                 n_skip=cfg.effective_frame_skip, seed=cfg.seed)
+        rr = stages.ransac_host_lists(cfg.ransac_model, src, kp_tpl, pt_off, cons.pt_off, pt_idx, n_tpl,
+                                      cfg.ransac_trials, cfg.ransac_threshold, cfg.spatial_rate,
+                                      cfg.effective_frame_skip, cfg.seed)
     if cfg.ransac_model == "affine":
         rr.params = rr.params[:, :2].contiguous()
     return rr

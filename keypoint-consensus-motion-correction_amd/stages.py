@@ -437,46 +437,57 @@ class RansacResult:
     best_trial: torch.Tensor   # [F] i32 (-1: none)
 
 
-def _ransac_two_point(entry: str, what: str, src, dst, pt_off, pt_off_host, pt_idx, src_frame_stride, trials,
-                      residual_threshold, spatial_rate, n_skip, seed, min_samples) -> RansacResult:
-    """The 2-sample models' launch (C entry ``entry``: kcmc_ransac_rigid / _similarity): checks,
-    the hypothesis tables of the frames' point counts, one launch over every frame."""
+def _ransac_launch(model: str, src, dst, pt_off, pt_idx, src_frame_stride, max_n, P, trials, residual_threshold,
+                   spatial_rate, n_skip, stream=None) -> RansacResult:
+    """One RANSAC launch over every frame of CSR point lists (the hypothesis tables are ready):
+    the result buffers, params [F, 2, 3] for the 2-sample models and [F, 3, 3] for the others,
+    and the model's C entry."""
+    dev = _device_of(src)
+    F = pt_off.numel() - 1
+    two_point = _lib.MODEL_MIN_SAMPLES[model] == 2
+    res = RansacResult(
+        params=torch.empty((F, 2, 3) if two_point else (F, 3, 3), dtype=torch.float64, device=dev),
+        inliers=torch.empty((P,), dtype=torch.uint8, device=dev),
+        n_inliers=torch.empty((F,), dtype=torch.int32, device=dev),
+        best_trial=torch.empty((F,), dtype=torch.int32, device=dev),
+    )
+    if F == 0:
+        return res
+    L = _lib.load()
+    if two_point:
+        entry, which = (L.kcmc_ransac_rigid if model == "euclidean" else L.kcmc_ransac_similarity), ()
+    else:
+        entry, which = L.kcmc_ransac_model, (_lib.MODEL_IDS[model],)
+    _lib.check(entry(
+        _ctx(dev).handle, *which, _ptr(src), _ptr(dst), _ptr(pt_idx), _ptr(pt_off), int(src_frame_stride), F,
+        int(max_n), int(trials), float(residual_threshold), float(spatial_rate), int(n_skip), _ptr(res.params),
+        _ptr(res.inliers), _ptr(res.n_inliers), _ptr(res.best_trial), _stream(dev, stream)))
+    return res
+
+
+def ransac_host_lists(model: str, src, dst, pt_off, pt_off_host, pt_idx, src_frame_stride, trials,
+                       residual_threshold, spatial_rate, n_skip, seed) -> RansacResult:
+    """RANSAC of any model on point lists whose offsets the host holds too (what ransac_rigid,
+    ransac_similarity and ransac_model run): the argument checks, skimage's ValueError, the
+    hypothesis tables of the frames' point counts, then the launch."""
     dev = _device_of(src)
     _require(src, "src", torch.float64, dev, 2)
     _require(dst, "dst", torch.float64, dev, 2)
     _require(pt_off, "pt_off", torch.int32, dev, 1)
     if pt_idx is not None:
         _require(pt_idx, "pt_idx", torch.int32, dev, 1)
-    if min_samples != 2:
-        raise ValueError(what)
+    ms = _lib.MODEL_MIN_SAMPLES[model]
     F = pt_off.numel() - 1
     pt_off_host = np.asarray(pt_off_host)
     _check_offsets(pt_off_host, F)
     ns = np.diff(pt_off_host)
     # skimage raises when a frame is not skipped but has N <= min_samples (fit.py:798-799)
-    bad = (ns >= n_skip) & (ns <= min_samples)
-    if bad.any():
+    if ((ns >= n_skip) & (ns <= ms)).any():
         raise ValueError("`min_samples` must be in range (0, <number-of-samples>)")
-    max_n = int(ns.max()) if F else 0
-    P = int(pt_off_host[-1]) if F else 0
-    res = RansacResult(
-        params=torch.empty((F, 2, 3), dtype=torch.float64, device=dev),
-        inliers=torch.empty((max(P, 0),), dtype=torch.uint8, device=dev),
-        n_inliers=torch.empty((F,), dtype=torch.int32, device=dev),
-        best_trial=torch.empty((F,), dtype=torch.int32, device=dev),
-    )
-    if F == 0:
-        return res
-    ctx = _ctx(dev)
-    L = _lib.load()
-    n_run = np.unique(ns[ns >= max(int(n_skip), 3)]).astype(np.int32)
-    _lib.check(L.kcmc_ransac_prepare(ctx.handle, _np_ptr(n_run), int(n_run.size), int(trials),
-                                     int(seed) & 0xFFFFFFFF))
-    _lib.check(getattr(L, entry)(
-        ctx.handle, _ptr(src), _ptr(dst), _ptr(pt_idx), _ptr(pt_off), int(src_frame_stride), F, max_n, int(trials),
-        float(residual_threshold), float(spatial_rate), int(n_skip), _ptr(res.params), _ptr(res.inliers),
-        _ptr(res.n_inliers), _ptr(res.best_trial), _stream(dev)))
-    return res
+    if F:
+        _ransac_prepare(dev, model, np.unique(ns[ns >= max(int(n_skip), ms + 1, 3)]), trials, seed)
+    return _ransac_launch(model, src, dst, pt_off, pt_idx, src_frame_stride, int(ns.max()) if F else 0,
+                          int(pt_off_host[-1]) if F else 0, trials, residual_threshold, spatial_rate, n_skip)
 
 
 def ransac_rigid(
@@ -498,9 +509,10 @@ def ransac_rigid(
     With ``pt_idx``: point k of frame f is src[f*src_frame_stride + pt_idx[k]] /
     dst[pt_idx[k]] (src = kp_ordered [F*n_tpl, 2], dst = template keypoints).
     """
-    return _ransac_two_point("kcmc_ransac_rigid", "rigid RANSAC uses min_samples=2 (EuclideanTransform, VA:312)",
-                             src, dst, pt_off, pt_off_host, pt_idx, src_frame_stride, trials, residual_threshold,
-                             spatial_rate, n_skip, seed, min_samples)
+    if min_samples != 2:
+        raise ValueError("rigid RANSAC uses min_samples=2 (EuclideanTransform, VA:312)")
+    return ransac_host_lists("euclidean", src, dst, pt_off, pt_off_host, pt_idx, src_frame_stride, trials,
+                              residual_threshold, spatial_rate, n_skip, seed)
 
 
 def ransac_similarity(
@@ -520,9 +532,10 @@ def ransac_similarity(
     """skimage ransac(SimilarityTransform, min_samples=2) per frame, all frames in one launch
     (K2s: the rigid kernel with the scale estimated, csrc/ransac.hip); arguments, addressing
     forms, skip / NaN conventions and result as ransac_rigid, params [F, 2, 3] = [scale R | t]."""
-    return _ransac_two_point("kcmc_ransac_similarity", "similarity RANSAC uses min_samples=2", src, dst, pt_off,
-                             pt_off_host, pt_idx, src_frame_stride, trials, residual_threshold, spatial_rate, n_skip,
-                             seed, min_samples)
+    if min_samples != 2:
+        raise ValueError("similarity RANSAC uses min_samples=2")
+    return ransac_host_lists("similarity", src, dst, pt_off, pt_off_host, pt_idx, src_frame_stride, trials,
+                              residual_threshold, spatial_rate, n_skip, seed)
 
 
 def ransac_model(
@@ -548,40 +561,20 @@ def ransac_model(
     if model not in ("affine", "projective"):
         raise ValueError(f"model must be 'affine' or 'projective' (got {model!r}); rigid: ransac_rigid, "
                          "similarity: ransac_similarity")
-    dev = _device_of(src)
-    _require(src, "src", torch.float64, dev, 2)
-    _require(dst, "dst", torch.float64, dev, 2)
-    _require(pt_off, "pt_off", torch.int32, dev, 1)
-    if pt_idx is not None:
-        _require(pt_idx, "pt_idx", torch.int32, dev, 1)
+    return ransac_host_lists(model, src, dst, pt_off, pt_off_host, pt_idx, src_frame_stride, trials,
+                              residual_threshold, spatial_rate, n_skip, seed)
+
+
+def _ransac_prepare(dev: torch.device, model: str, n_run: np.ndarray, trials: int, seed: int) -> None:
+    """Make the model's hypothesis tables of the point counts n_run current on the device."""
+    n_run = np.ascontiguousarray(n_run, dtype=np.int32)
     ms = _lib.MODEL_MIN_SAMPLES[model]
-    F = pt_off.numel() - 1
-    pt_off_host = np.asarray(pt_off_host)
-    _check_offsets(pt_off_host, F)
-    ns = np.diff(pt_off_host)
-    bad = (ns >= n_skip) & (ns <= ms)
-    if bad.any():
-        raise ValueError("`min_samples` must be in range (0, <number-of-samples>)")
-    max_n = int(ns.max()) if F else 0
-    P = int(pt_off_host[-1]) if F else 0
-    res = RansacResult(
-        params=torch.empty((F, 3, 3), dtype=torch.float64, device=dev),
-        inliers=torch.empty((max(P, 0),), dtype=torch.uint8, device=dev),
-        n_inliers=torch.empty((F,), dtype=torch.int32, device=dev),
-        best_trial=torch.empty((F,), dtype=torch.int32, device=dev),
-    )
-    if F == 0:
-        return res
-    ctx = _ctx(dev)
     L = _lib.load()
-    n_run = np.unique(ns[ns >= max(int(n_skip), ms + 1)]).astype(np.int32)
-    _lib.check(L.kcmc_ransac_prepare_samples(ctx.handle, ms, _np_ptr(n_run), int(n_run.size), int(trials),
-                                             int(seed) & 0xFFFFFFFF))
-    _lib.check(L.kcmc_ransac_model(
-        ctx.handle, _lib.MODEL_IDS[model], _ptr(src), _ptr(dst), _ptr(pt_idx), _ptr(pt_off), int(src_frame_stride), F,
-        max_n, int(trials), float(residual_threshold), float(spatial_rate), int(n_skip), _ptr(res.params),
-        _ptr(res.inliers), _ptr(res.n_inliers), _ptr(res.best_trial), _stream(dev)))
-    return res
+    args = (_np_ptr(n_run), int(n_run.size), int(trials), int(seed) & 0xFFFFFFFF)
+    if ms == 2:
+        _lib.check(L.kcmc_ransac_prepare(_ctx(dev).handle, *args))
+    else:
+        _lib.check(L.kcmc_ransac_prepare_samples(_ctx(dev).handle, ms, *args))
 
 
 def ransac_prepare_range(device, model: str, n_lo: int, n_hi: int, trials: int = 1000, seed: int = 42) -> None:
@@ -592,19 +585,10 @@ def ransac_prepare_range(device, model: str, n_lo: int, n_hi: int, trials: int =
     (ransac_rigid / ransac_model, or an aligner with another RANDOM_SEED) may have
     replaced it since; the C side regenerates only the counts it lacks and re-uploads
     only when the set changed, so a repeat call is one host loop over the range."""
-    dev = torch.device(device)
-    ctx = _ctx(dev)
-    ms = _lib.MODEL_MIN_SAMPLES[model]
-    n_lo = max(int(n_lo), ms + 1, 3)
+    n_lo = max(int(n_lo), _lib.MODEL_MIN_SAMPLES[model] + 1, 3)
     if int(n_hi) < n_lo:
         return
-    n_run = np.arange(n_lo, int(n_hi) + 1, dtype=np.int32)
-    L = _lib.load()
-    seed = int(seed) & 0xFFFFFFFF
-    if ms == 2:
-        _lib.check(L.kcmc_ransac_prepare(ctx.handle, _np_ptr(n_run), int(n_run.size), int(trials), seed))
-    else:
-        _lib.check(L.kcmc_ransac_prepare_samples(ctx.handle, ms, _np_ptr(n_run), int(n_run.size), int(trials), seed))
+    _ransac_prepare(torch.device(device), model, np.arange(n_lo, int(n_hi) + 1), trials, seed)
 
 
 def ransac_lists(model: str, src: torch.Tensor, dst: torch.Tensor, pt_off: torch.Tensor, pt_idx: torch.Tensor,
@@ -615,33 +599,8 @@ def ransac_lists(model: str, src: torch.Tensor, dst: torch.Tensor, pt_off: torch
     the tables of every count in [n_skip, max_n] must be ready (ransac_prepare_range).
     params [F, 2, 3] (euclidean, similarity) or [F, 3, 3] (affine / projective), as
     ransac_rigid / ransac_similarity / ransac_model."""
-    dev = _device_of(src)
-    F = pt_off.numel() - 1
-    P = pt_idx.numel()
-    res = RansacResult(
-        params=torch.empty((F, 2, 3) if model in ("euclidean", "similarity") else (F, 3, 3), dtype=torch.float64,
-                           device=dev),
-        inliers=torch.empty((max(P, 1),), dtype=torch.uint8, device=dev),
-        n_inliers=torch.empty((F,), dtype=torch.int32, device=dev),
-        best_trial=torch.empty((F,), dtype=torch.int32, device=dev),
-    )
-    if F == 0:
-        return res
-    L = _lib.load()
-    ctx = _ctx(dev).handle
-    st = _stream(dev, stream)
-    if model in ("euclidean", "similarity"):
-        entry = L.kcmc_ransac_rigid if model == "euclidean" else L.kcmc_ransac_similarity
-        _lib.check(entry(
-            ctx, _ptr(src), _ptr(dst), _ptr(pt_idx), _ptr(pt_off), int(src_frame_stride), F, int(max_n), int(trials),
-            float(residual_threshold), float(spatial_rate), int(n_skip), _ptr(res.params), _ptr(res.inliers),
-            _ptr(res.n_inliers), _ptr(res.best_trial), st))
-    else:
-        _lib.check(L.kcmc_ransac_model(
-            ctx, _lib.MODEL_IDS[model], _ptr(src), _ptr(dst), _ptr(pt_idx), _ptr(pt_off), int(src_frame_stride), F,
-            int(max_n), int(trials), float(residual_threshold), float(spatial_rate), int(n_skip), _ptr(res.params),
-            _ptr(res.inliers), _ptr(res.n_inliers), _ptr(res.best_trial), st))
-    return res
+    return _ransac_launch(model, src, dst, pt_off, pt_idx, src_frame_stride, max_n, max(pt_idx.numel(), 1), trials,
+                          residual_threshold, spatial_rate, n_skip, stream)
 
 
 # ----------------------------------------------------------------------- K3
@@ -735,13 +694,6 @@ def warp_field_u16(frames: torch.Tensor, affines: torch.Tensor, field_q: torch.T
     _lib.check(L.kcmc_warp_field_u16(_ctx(dev).handle, _ptr(frames), _ptr(out), _ptr(affines), _ptr(field_q), F, H, W,
                                      gy, gx, int(bool(inverse_map)), _stream(dev, stream)))
     return out
-
-
-def _warp_shape(frames_shape) -> Tuple[int, int, int, int]:
-    if len(frames_shape) not in (3, 4):
-        raise ValueError("frames must be [F, H, W] or [F, H, W, C]")
-    F, H, W = (int(v) for v in frames_shape[:3])
-    return F, H, W, 1 if len(frames_shape) == 3 else int(frames_shape[3])
 
 
 # ------------------------------------------------------------ f2: normalisation
