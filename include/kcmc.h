@@ -382,7 +382,10 @@ int kcmc_lut_u16_to_u8(kcmc_ctx* ctx, const uint16_t* src_dev, unsigned long lon
  * pattern_dev [32][512][2] i8 and bin_cs_dev [32][2] f64 from kcmc_amd/orb.py;
  * edge >= 16.  Outputs per frame, in candidate order (64x16 tiles row-major, raster
  * inside a tile): out_kp_dev [n_frames, n_features, 2] f64 (x, y),
- * out_des_dev [n_frames, n_features, 32] u8, out_count_dev [n_frames] i32. */
+ * out_des_dev [n_frames, n_features, 32] u8, out_count_dev [n_frames] i32.
+ * frames_dev needs no alignment (4-byte staging loads are used only when W % 4 == 0 and
+ * frames_dev is 4-byte aligned; otherwise byte loads, same result).  n_features == 0
+ * needs only frames_dev and out_count_dev (zeroed); the other pointers may then be NULL. */
 int kcmc_orb_detect(kcmc_ctx* ctx, const uint8_t* frames_dev, int n_frames, int H, int W, int threshold,
                     int n_features, double harris_k, int edge, const int8_t* pattern_dev,
                     const double* bin_cs_dev, double* out_kp_dev, uint8_t* out_des_dev,

@@ -119,8 +119,9 @@ __device__ __forceinline__ int fast_score9(const uint8_t (*img)[kPW], int py, in
 // stored per tile, in list order.
 // 8 waves per SIMD (<= 64 VGPRs, no spill): the workgroups are barrier- and latency-bound,
 // and the eighth wave slot took 15.4 -> 14.8 ms per 2000 c2 frames (profiles/r06_orb_subtiles_ab.txt)
+// words: the launcher's staging flag (W % 4 == 0 and frames 4-byte aligned).
 __global__ __launch_bounds__(kThreads, 8) void orb_candidates_kernel(const uint8_t* __restrict__ frames, int H, int W,
-                                                                  int threshold, double harris_k, int edge,
+                                                                  int words, int threshold, double harris_k, int edge,
                                                                   uint64_t* __restrict__ cand_key,
                                                                   uint32_t* __restrict__ cand_pos,
                                                                   int32_t* __restrict__ cand_cnt) {
@@ -137,8 +138,8 @@ __global__ __launch_bounds__(kThreads, 8) void orb_candidates_kernel(const uint8
   const int tid = threadIdx.x;
   const uint8_t* I = frames + (size_t)f * H * W;
 
-  // (1) staging: 4-byte words where the row is aligned (x0 - 4 is a multiple of 4)
-  if ((W & 3) == 0) {
+  // (1) staging: 4-byte words where every row is aligned (x0 - 4 is a multiple of 4)
+  if (words) {
     for (int i = tid; i < kPH * (kPW / 4); i += kThreads) {
       const int r = i / (kPW / 4), c = 4 * (i - r * (kPW / 4));
       const int y = y0 - kHalo + r, x = x0 - kHalo + c;
@@ -413,7 +414,7 @@ __global__ __launch_bounds__(kThreads) void orb_describe_kernel(const uint8_t* _
                                                                 const int32_t* __restrict__ kp_n, int n_features,
                                                                 const int8_t* __restrict__ pattern,
                                                                 const double* __restrict__ bin_cs, int f_base,
-                                                                uint8_t* __restrict__ out_des) {
+                                                                int words, uint8_t* __restrict__ out_des) {
   __shared__ uint32_t patch[kThreads / 64][kPatch * kPatchWords];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int f = blockIdx.y;
@@ -431,7 +432,7 @@ __global__ __launch_bounds__(kThreads) void orb_describe_kernel(const uint8_t* _
     const int r = i / kPatchWords, c = i - r * kPatchWords;
     const uint8_t* src = I + (size_t)(y - 15 + r) * W + bx + 4 * c;
     uint32_t v;
-    if ((W & 3) == 0) {
+    if (words) {
       v = *reinterpret_cast<const uint32_t*>(src);
     } else {
       v = 0;
@@ -490,7 +491,8 @@ extern "C" int kcmc_orb_detect(kcmc_ctx* ctx, const uint8_t* frames, int n_frame
   if (!ctx) return fail(KCMC_EINVAL, "kcmc_orb_detect: ctx is NULL");
   if (n_frames < 0 || H < 0 || W < 0 || n_features < 0) return fail(KCMC_EINVAL, "kcmc_orb_detect: negative size");
   if (n_frames == 0) return KCMC_OK;
-  if (!frames || !pattern || !bin_cs || !out_kp || !out_des || !out_count)
+  // n_features == 0 writes only the counts: the empty out_kp / out_des (and the tables) may be NULL
+  if (!frames || !out_count || (n_features > 0 && (!pattern || !bin_cs || !out_kp || !out_des)))
     return fail(KCMC_EINVAL, "kcmc_orb_detect: NULL pointer");
   if (edge < 16) return fail(KCMC_EINVAL, "kcmc_orb_detect: edge must be >= 16 (orientation disc + BRIEF patch)");
   if (H > 65535 || W > 65535) return fail(KCMC_EUNSUPPORTED, "kcmc_orb_detect: H, W must be < 65536");
@@ -499,6 +501,9 @@ extern "C" int kcmc_orb_detect(kcmc_ctx* ctx, const uint8_t* frames, int n_frame
   KCMC_TRY(hip_check(hipMemsetAsync(out_count, 0, (size_t)n_frames * sizeof(int32_t), s), "hipMemsetAsync"));
   if (n_features == 0 || H < 2 * edge + 1 || W < 2 * edge + 1) return KCMC_OK;
   const int ntx = ceil_div(W, kTW), nty = ceil_div(H, kTH), ntiles = ntx * nty;
+  // 4-byte staging loads need every row start aligned: W % 4 == 0 and an aligned base
+  // (a view into a larger buffer may start anywhere); otherwise the byte paths
+  const int words = (W & 3) == 0 && ((uintptr_t)frames & 3) == 0;
   // frames are processed in batches so that the candidate slots stay a bounded workspace
   const size_t slots = (size_t)ntiles * kSlots;
   const size_t per_frame = 2 * slots * (sizeof(uint64_t) + sizeof(uint32_t)) + (size_t)ntiles * 2 * sizeof(int32_t) + 4;
@@ -518,7 +523,7 @@ extern "C" int kcmc_orb_detect(kcmc_ctx* ctx, const uint8_t* frames, int n_frame
   for (int f0 = 0; f0 < n_frames && rc == KCMC_OK; f0 += batch) {
     const int nb = std::min(batch, n_frames - f0);
     const uint8_t* fr = frames + (size_t)f0 * H * W;
-    hipLaunchKernelGGL(orb_candidates_kernel, dim3(ntx, ceil_div(nty, kSub), nb), dim3(kThreads), 0, s, fr, H, W, threshold, harris_k,
+    hipLaunchKernelGGL(orb_candidates_kernel, dim3(ntx, ceil_div(nty, kSub), nb), dim3(kThreads), 0, s, fr, H, W, words, threshold, harris_k,
                        edge, ckey, cpos, ccnt);
     hipLaunchKernelGGL(orb_offsets_kernel, dim3(nb), dim3(kThreads), 0, s, ccnt, ntiles, toff, ctot);
     hipLaunchKernelGGL(orb_gather_kernel, dim3(ceil_div(ntiles, 4 * 8), nb), dim3(kThreads), 0, s, ckey, cpos, ccnt,
@@ -526,7 +531,7 @@ extern "C" int kcmc_orb_detect(kcmc_ctx* ctx, const uint8_t* frames, int n_frame
     hipLaunchKernelGGL(orb_select_kernel, dim3(nb), dim3(kThreads), 0, s, lkey, lpos, ctot, ntiles, n_features, out_kp,
                        kpos, out_count, f0);
     hipLaunchKernelGGL(orb_describe_kernel, dim3(ceil_div(n_features, kThreads / 64), nb), dim3(kThreads), 0, s, fr, H,
-                       W, kpos, out_count, n_features, pattern, bin_cs, f0, out_des);
+                       W, kpos, out_count, n_features, pattern, bin_cs, f0, words, out_des);
     rc = launch_check("orb kernels");
   }
   const int rc2 = workspace_free(ctx, ws, s);

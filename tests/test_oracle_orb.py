@@ -55,13 +55,20 @@ def test_fast_score_and_harris_match_python():
             assert L.kcmc_oracle_harris(p, W, x, y, 0.04) == harris_py(img, x, y)
 
 
-def detect_py(img, n_features=500, threshold=20, k=0.04, edge=16):
+def score_map_py(img):
+    """Raw FAST-9 scores of every pixel at least 3 px inside the frame (-1000 elsewhere)."""
     H, W = img.shape
-    score = np.zeros((H, W), np.int64)
+    score = np.full((H, W), -1000, np.int64)
     for y in range(3, H - 3):
         for x in range(3, W - 3):
-            s = fast_score_py(img, x, y)
-            score[y, x] = s if s > threshold else 0
+            score[y, x] = fast_score_py(img, x, y)
+    return score
+
+
+def candidates_py(img, raw, threshold=20, k=0.04, edge=16):
+    """NMS survivors in candidate order (64x16 tiles row-major, raster inside): (R, x, y)."""
+    H, W = img.shape
+    score = np.where(raw > threshold, raw, 0)
     cands = []
     for ty in range(0, H, 16):
         for tx in range(0, W, 64):
@@ -74,49 +81,77 @@ def detect_py(img, n_features=500, threshold=20, k=0.04, edge=16):
                              for dy in (-1, 0, 1) for dx in (-1, 0, 1) if dx or dy)
                     if ok:
                         cands.append((harris_py(img, x, y, k), x, y))
-    if len(cands) > n_features:
-        T = sorted((c[0] for c in cands), reverse=True)[n_features - 1]
-        n_gt = sum(c[0] > T for c in cands)
-        kept, ties = [], 0
-        for c in cands:
-            if c[0] > T:
-                kept.append(c)
-            elif c[0] == T and ties < n_features - n_gt:
-                kept.append(c)
-                ties += 1
-        cands = kept
-    pat, cs = orb.rotated_patterns(), orb.bin_edges()
+    return cands
+
+
+def select_py(cands, n_features):
+    """The n_features largest responses; ties at the cut in candidate order."""
+    if len(cands) <= n_features:
+        return cands
+    if n_features <= 0:
+        return []
+    T = sorted((c[0] for c in cands), reverse=True)[n_features - 1]
+    n_gt = sum(c[0] > T for c in cands)
+    kept, ties = [], 0
+    for c in cands:
+        if c[0] > T:
+            kept.append(c)
+        elif c[0] == T and ties < n_features - n_gt:
+            kept.append(c)
+            ties += 1
+    return kept
+
+
+def moments_py(img, x, y):
+    m10 = m01 = 0
+    for dy in range(-15, 16):
+        for dx in range(-15, 16):
+            if dx * dx + dy * dy <= 225:
+                m10 += dx * int(img[y + dy, x + dx])
+                m01 += dy * int(img[y + dy, x + dx])
+    return m10, m01
+
+
+def bin_py(m10, m01):
+    if m10 == 0 and m01 == 0:
+        return 0
+    cs = orb.bin_edges()
+    b = math.floor(math.atan2(m01, m10) / 0.19634954084936207) & 31
+    b1 = (b + 1) & 31
+    if m01 * cs[b, 0] - m10 * cs[b, 1] < 0:
+        b = (b + 31) & 31
+    elif m01 * cs[b1, 0] - m10 * cs[b1, 1] >= 0:
+        b = b1
+    return b
+
+
+_W5 = np.outer([1, 4, 6, 4, 1], [1, 4, 6, 4, 1])
+
+
+def describe_py(img, x, y):
+    """The 32-byte steered-BRIEF descriptor of the keypoint at (x, y)."""
+    pat = orb.rotated_patterns().astype(np.int64)  # int8 + a coordinate above 127 would overflow
     I = img.astype(np.int64)
-    w = np.array([1, 4, 6, 4, 1])
-    ww = np.outer(w, w)
 
     def sm(x, y):
-        return (int((ww * I[y - 2:y + 3, x - 2:x + 3]).sum()) + 128) >> 8
+        return (int((_W5 * I[y - 2:y + 3, x - 2:x + 3]).sum()) + 128) >> 8
 
-    kps, des = [], []
-    for _, x, y in cands:
-        m10 = m01 = 0
-        for dy in range(-15, 16):
-            for dx in range(-15, 16):
-                if dx * dx + dy * dy <= 225:
-                    m10 += dx * int(I[y + dy, x + dx])
-                    m01 += dy * int(I[y + dy, x + dx])
-        if m10 == 0 and m01 == 0:
-            b = 0
-        else:
-            b = math.floor(math.atan2(m01, m10) / 0.19634954084936207) & 31
-            b1 = (b + 1) & 31
-            if m01 * cs[b, 0] - m10 * cs[b, 1] < 0:
-                b = (b + 31) & 31
-            elif m01 * cs[b1, 0] - m10 * cs[b1, 1] >= 0:
-                b = b1
-        d = np.zeros(32, np.uint8)
-        for i in range(256):
-            (px, py), (qx, qy) = pat[b, 2 * i], pat[b, 2 * i + 1]
-            if sm(x + px, y + py) < sm(x + qx, y + qy):
-                d[i // 8] |= 1 << (i % 8)
-        kps.append((x, y))
-        des.append(d)
+    b = bin_py(*moments_py(img, x, y))
+    d = np.zeros(32, np.uint8)
+    for i in range(256):
+        (px, py), (qx, qy) = pat[b, 2 * i], pat[b, 2 * i + 1]
+        if sm(x + px, y + py) < sm(x + qx, y + qy):
+            d[i // 8] |= 1 << (i % 8)
+    return d
+
+
+def detect_py(img, n_features=500, threshold=20, k=0.04, edge=16, raw=None, describe=describe_py):
+    """The detector's definition, step by step.  raw (score_map_py(img)) and describe let
+    a caller that runs many parameter sets on one image reuse the parameter-free parts."""
+    raw = score_map_py(img) if raw is None else raw
+    cands = select_py(candidates_py(img, raw, threshold, k, edge), n_features)
+    kps = [(x, y) for _, x, y in cands]
+    des = [describe(img, x, y) for _, x, y in cands]
     return np.array(kps, np.float64).reshape(-1, 2), np.array(des, np.uint8).reshape(-1, 32)
 
 
