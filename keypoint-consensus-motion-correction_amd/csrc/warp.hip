@@ -24,7 +24,9 @@
 //
 // One-channel frames with W % 8 == 0 and a box that fits a fixed 144-pixel LDS pitch (the
 // near-identity maps of motion correction) take a leaner form of the same path (mode 3,
-// fast_rows): scalar per-row origins from a per-frame table, immediate-offset taps, buffer
+// fast_rows): the box staged by range-checked buffer loads at a constant row stride per
+// thread (FastStage: the descriptor's range check is the zero border, one add per pass),
+// scalar per-row origins from a per-frame table, immediate-offset taps, buffer
 // stores, and a per-tile choice of blend from the staged values (exact integer blend with
 // no range check when every value is < 16384; with a few bright values the integer blend
 // and OpenCV's float blend only for rows with a sum near a rounding tie; the float blend on
@@ -90,7 +92,6 @@ template <class Cfg>
 struct Fast {
   static constexpr int kRows = (Cfg::kLdsElems - 8) / kFastPitch;  // the last 16 bytes: per-wave flags
   static constexpr int kFlagWord = Cfg::kLdsElems / 2 - 4;          // uint32 index of the flags
-  static constexpr int kPasses = (kRows * kFastChunks + kThreads - 1) / kThreads;
 };
 
 struct Box {
@@ -246,32 +247,82 @@ __device__ __forceinline__ uint32_t tap(const uint16_t* stile, int i) { return s
 __device__ __forceinline__ uint32_t bfe_11_5(uint32_t v) { return __builtin_amdgcn_ubfe(v, 11, 5); }
 
 
-// Fast-path staging: chunk q = tid + 256k of the box in row-major order at kFastChunks
-// chunks per row (LDS offset 16q); chunks right of the box's own pitch are left unwritten
-// (never read).
+// Fast-path staging.  Thread tid owns chunk column c = tid % kFastChunks and the box rows
+// r0 + kStep k (r0 = tid / kFastChunks, kStep = 14: 252 of the 256 threads), so the row-major
+// LDS slot of pass k is 16 tid + an immediate, and the source byte offset of pass k is the
+// thread's first offset plus k times a wave-uniform stride: one add per pass.  The loads are
+// raw buffer loads through one descriptor per tile, base = the frame, num_records = the
+// bytes of the frame down to the box's last row; the hardware range check of voffset then
+// returns the zeros of BORDER_CONSTANT for rows above the frame (the 32-bit offset wraps
+// beyond 2^31 > num_records: H, W < 2^15, |row| <= 30000), for rows below it and for rows
+// below the box (not fetched), and a row never reads the neighbouring frame.  The column
+// test is paid once: a thread whose chunk is outside the box's pitch or the frame's columns
+// (or one of the 4 spare threads) starts at offset 2^31, out of range for every pass.  So
+// the load passes hold no exec-mask branch, no zero-initialised registers and no 64-bit
+// address arithmetic.  kPasses whole passes cover rows 0 .. kPasses * kStep - 1 (69); a box
+// with more rows (the 71st, rare) stages the rest in a tail pass behind a wave-uniform branch.
 template <class Cfg>
-__device__ __forceinline__ void fast_stage_issue(const uint16_t* __restrict__ S, int ax0, int sy0, int cpr, int rows,
-                                                 int H, int W, int tid, uint4 (&chunk)[Fast<Cfg>::kPasses]) {
-#pragma unroll
-  for (int k = 0; k < Fast<Cfg>::kPasses; ++k) {
-    const int q = tid + kThreads * k;
-    const int r = q / kFastChunks, c = q - r * kFastChunks;
-    const int gy = sy0 + r, gx = ax0 + 8 * c;
-    chunk[k] = make_uint4(0u, 0u, 0u, 0u);
-    if (r < rows && c < cpr && (unsigned)gx < (unsigned)W && (unsigned)gy < (unsigned)H)
-      chunk[k] = *reinterpret_cast<const uint4*>(S + (size_t)gy * W + gx);
-  }
+struct FastStage {
+  static constexpr int kStep = kThreads / kFastChunks;        // box rows per pass (14)
+  static constexpr int kUsed = kStep * kFastChunks;           // staging threads (252)
+  static constexpr int kPasses = Fast<Cfg>::kRows / kStep;    // whole passes (5)
+  static constexpr int kTailRows = Fast<Cfg>::kRows - kPasses * kStep;  // rows of the tail pass (1)
+  static_assert(kTailRows < kStep && kTailRows * kFastChunks <= kThreads, "one tail pass");
+};
+
+struct FastSrc {
+  __amdgpu_buffer_rsrc_t rsrc;
+  uint32_t voff;  // byte offset of the thread's chunk in box row r0 (2^31: never in range)
+  uint32_t step;  // bytes of kStep frame rows (wave-uniform)
+};
+
+__device__ __forceinline__ uint4 fast_load(const FastSrc& fs, int k) {
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(fs.rsrc, fs.voff + (uint32_t)k * fs.step, 0, 0);
+  return make_uint4(v[0], v[1], v[2], v[3]);
 }
 
 template <class Cfg>
-__device__ __forceinline__ void fast_stage_land(uint16_t* stile, int cpr, int rows, int tid,
-                                                const uint4 (&chunk)[Fast<Cfg>::kPasses]) {
+__device__ __forceinline__ FastSrc fast_stage_issue(const uint16_t* __restrict__ S, int ax0, int sy0, int cpr,
+                                                    int rows, int H, int W, int tid,
+                                                    uint4 (&chunk)[FastStage<Cfg>::kPasses]) {
+  const int r0 = tid / kFastChunks, c = tid - r0 * kFastChunks;
+  const int gx = ax0 + 8 * c;
+  const bool col_ok = c < cpr && (unsigned)gx < (unsigned)W && tid < FastStage<Cfg>::kUsed;
+  FastSrc fs;
+  // |sy0 + r0| and W fit 24 bits; the byte offset of a row above the frame wraps (see above)
+  fs.voff = col_ok ? 2u * (uint32_t)(__mul24(sy0 + r0, W) + gx) : 0x80000000u;
+  fs.step = 2u * FastStage<Cfg>::kStep * (uint32_t)W;
+  fs.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(S), 0, 2 * min(H, sy0 + rows) * W, 0x00020000);
 #pragma unroll
-  for (int k = 0; k < Fast<Cfg>::kPasses; ++k) {
-    const int q = tid + kThreads * k;
-    const int r = q / kFastChunks, c = q - r * kFastChunks;
-    if (r < rows && c < cpr) reinterpret_cast<uint4*>(stile)[q] = chunk[k];
+  for (int k = 0; k < FastStage<Cfg>::kPasses; ++k) chunk[k] = fast_load(fs, k);
+  return fs;
+}
+
+__device__ __forceinline__ uint32_t bright_chunks(const uint4& v) {
+  return __builtin_popcountll(__builtin_amdgcn_ballot_w64(((v.x | v.y | v.z | v.w) & 0xc000c000u) != 0));
+}
+
+// Lands the passes in LDS and returns the wave's count of bright (>= 16384) chunks.  Rows
+// below the box and chunks right of its pitch land as zeros (never read).
+template <class Cfg>
+__device__ __forceinline__ uint32_t fast_stage_land(uint16_t* stile, const FastSrc& fs, int rows, int tid,
+                                                    const uint4 (&chunk)[FastStage<Cfg>::kPasses]) {
+  using St = FastStage<Cfg>;
+  uint4* slot = reinterpret_cast<uint4*>(stile) + tid;
+  uint32_t nb = 0;
+  if (tid < St::kUsed) {
+#pragma unroll
+    for (int k = 0; k < St::kPasses; ++k) slot[k * St::kUsed] = chunk[k];
   }
+#pragma unroll
+  for (int k = 0; k < St::kPasses; ++k) nb += bright_chunks(chunk[k]);
+  if (St::kTailRows > 0 && rows > St::kPasses * St::kStep) {  // wave-uniform
+    const uint4 t = fast_load(fs, St::kPasses);  // rows past the box are out of range: zeros
+    if (tid < St::kTailRows * kFastChunks) slot[St::kPasses * St::kUsed] = t;
+    nb += bright_chunks(t);
+  }
+  return nb;
 }
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -810,7 +861,10 @@ __global__ __launch_bounds__(256) void warp_plan_kernel(const double* __restrict
     for (int k = 0; k < 6; ++k) minv[6 * (size_t)f + k] = M[k];
   Box b = source_box<Cfg, C>(M, xb, yb, H, W);
   if constexpr (C == 1) {
-    if ((W & 7) == 0 && b.mode == 0 && b.pitch <= kFastPitch && b.rows <= Fast<Cfg>::kRows) b.mode = 3;
+    // 2 H W < 2^31: the frame fits the range of the fast path's buffer descriptors
+    if ((W & 7) == 0 && 2ll * H * W < (1ll << 31) && b.mode == 0 && b.pitch <= kFastPitch &&
+        b.rows <= Fast<Cfg>::kRows)
+      b.mode = 3;
   } else if constexpr (C == 3 || C == 4) {
     if ((W & 7) == 0 && b.mode == 0 && b.pitch <= FastC<Cfg, C>::kPitch && b.rows <= FastC<Cfg, C>::kRows) b.mode = 3;
   }
@@ -847,17 +901,12 @@ __global__ __launch_bounds__(kThreads) __attribute__((target("no-unaligned-acces
   if constexpr (C == 1) {
     if (box.mode == 3) {
       const int cpr = box.pitch >> 3;
-      uint4 fchunk[Fast<Cfg>::kPasses];
-      fast_stage_issue<Cfg>(S, box.ax0, box.sy0, cpr, box.rows, H, W, tid, fchunk);  // loads first
+      uint4 fchunk[FastStage<Cfg>::kPasses];
+      const FastSrc fs = fast_stage_issue<Cfg>(S, box.ax0, box.sy0, cpr, box.rows, H, W, tid, fchunk);  // loads first
       int ad[2], bd[2];
       lane_cols(minv + 6 * (size_t)f, xb, W, lane, ad, bd);
-      fast_stage_land<Cfg>(stile, cpr, box.rows, tid, fchunk);
-      // bright (>= 16384) staged chunks of the box, counted per wave into the flag words
-      uint32_t nb = 0;
-#pragma unroll
-      for (int k = 0; k < Fast<Cfg>::kPasses; ++k)
-        nb += __builtin_popcountll(__builtin_amdgcn_ballot_w64(
-            ((fchunk[k].x | fchunk[k].y | fchunk[k].z | fchunk[k].w) & 0xc000c000u) != 0));
+      // the box lands; its bright chunks are counted per wave into the flag words
+      const uint32_t nb = fast_stage_land<Cfg>(stile, fs, box.rows, tid, fchunk);
       uint32_t* flags = reinterpret_cast<uint32_t*>(stile) + Fast<Cfg>::kFlagWord;
       if (lane == 0) flags[wave] = nb;
       __syncthreads();
