@@ -391,6 +391,46 @@ int kcmc_orb_detect(kcmc_ctx* ctx, const uint8_t* frames_dev, int n_frames, int 
                     const double* bin_cs_dev, double* out_kp_dev, uint8_t* out_des_dev,
                     int32_t* out_count_dev, kcmc_stream_t stream);
 
+/* ------------------------------------------------------ f1: the scale pyramid
+ * Build-defined like the detector; the host computes every size and quota as integers
+ * (kcmc_amd/orb.py level_sizes / level_quotas) and the kernels receive integers only.
+ *
+ * The exact bilinear resize that makes level l from level l - 1: src_dev [n_frames, H, W]
+ * u8 -> dst_dev [n_frames, dst_h, dst_w] u8, any sizes in [1, 65535] (upscaling too), no
+ * alignment requirement, at most 65535 frames per call.  Per axis, source length n,
+ * destination length m, destination index x:
+ *   num = (2x + 1) n - m, den = 2m, i = floor(num / den),
+ *   a = ((num - i den) 2048 + m) / den (integer division);
+ *   i < 0 -> i = 0, a = 0;  i >= n - 1 -> i = n - 1, a = 0 (second tap clamped to n - 1);
+ *   dst = (sum of the 4 taps x (2048 - a | a)(2048 - b | b) + 2^21) >> 22.
+ * m == n is the identity; an exact 2:1 is (sum of the 2x2 + 2) >> 2. */
+int kcmc_resize_u8(kcmc_ctx* ctx, const uint8_t* src_dev, int n_frames, int H, int W, uint8_t* dst_dev,
+                   int dst_h, int dst_w, kcmc_stream_t stream);
+
+/* kcmc_orb_detect on every level of a scale pyramid.  Host arrays level_h, level_w,
+ * level_quota [n_levels], n_levels in [1, 8]: level 0 must be (H, W), sizes >= 1 and
+ * non-increasing, quotas >= 0 with sum n_features (else KCMC_EINVAL, before any launch).
+ * orb.py: H_l = rint(H / scale_factor^l) (half to even, doubles), W_l alike; with
+ * f = 1 / scale_factor and d_0 = n_features (1 - f) / (1 - f^n_levels), level
+ * l < n_levels - 1 gets rint(d_l), d_{l+1} = d_l f, the last max(n_features - sum, 0).
+ * Level l is kcmc_resize_u8 of level l - 1 (level 0: frames_dev).  Every level runs the
+ * detector above unchanged on its image with its quota as the budget (same threshold,
+ * harris_k, edge, tables); a level with H_l or W_l < 2 edge + 1, or quota 0, yields nothing
+ * and its quota is not redistributed.  Output rows: level 0 first, each level in its
+ * candidate order, packed without gaps; out_count_dev = the sum of the levels' counts; rows
+ * at or past it are undefined.  Coordinates are mapped to level 0 through the resize's own
+ * pixel map, one correctly rounded double division per axis:
+ *   x0 = ((2 x_l + 1) W - W_l) / (2 W_l),  y0 = ((2 y_l + 1) H - H_l) / (2 H_l)
+ * (level 0: x0 = x_l exactly; not OpenCV's x * scale, which the rounding of the level sizes
+ * biases).  out_level_dev [n_frames, n_features] u8 names each row's level.  The levels
+ * live in the context workspace; frames are batched so that it stays bounded. */
+int kcmc_orb_detect_pyramid(kcmc_ctx* ctx, const uint8_t* frames_dev, int n_frames, int H, int W, int threshold,
+                            int n_features, double harris_k, int edge, const int8_t* pattern_dev,
+                            const double* bin_cs_dev, int n_levels, const int32_t* level_h,
+                            const int32_t* level_w, const int32_t* level_quota, double* out_kp_dev,
+                            uint8_t* out_des_dev, uint8_t* out_level_dev, int32_t* out_count_dev,
+                            kcmc_stream_t stream);
+
 /* ----------------------------------------------------- f4: spatial downsample
  * cv2.pyrDown(frame, dstsize=(dst_w, dst_h)) of every uint8 frame (replaces the per-frame
  * host calls of VideoAligner._downsample, VA:501-503): 5x5 binomial (1,4,6,4,1)^2 / 256,

@@ -55,6 +55,8 @@ EXPORTED_SYMBOLS = (
     "kcmc_histogram_u16",
     "kcmc_lut_u16_to_u8",
     "kcmc_orb_detect",
+    "kcmc_resize_u8",
+    "kcmc_orb_detect_pyramid",
     "kcmc_pyr_down_u8",
     "kcmc_stack_sum_u16",
     "kcmc_frame_stats_u16",
@@ -123,6 +125,8 @@ _SIGNATURES = {
     "kcmc_histogram_u16": ([P, P, ctypes.c_ulonglong, I, I, P, P], I),
     "kcmc_lut_u16_to_u8": ([P, P, ctypes.c_ulonglong, P, P, P], I),
     "kcmc_orb_detect": ([P, P, I, I, I, I, I, D, I, P, P, P, P, P, P], I),
+    "kcmc_resize_u8": ([P, P, I, I, I, P, I, I, P], I),
+    "kcmc_orb_detect_pyramid": ([P, P, I, I, I, I, I, D, I, P, P, I, P, P, P, P, P, P, P, P], I),
     "kcmc_pyr_down_u8": ([P, P, I, I, I, P, I, I, P], I),
     "kcmc_stack_sum_u16": ([P, P, I, ctypes.c_ulonglong, P, P, P], I),
     "kcmc_frame_stats_u16": ([P, P, I, I, I, P, I, I, I, I, P, P], I),

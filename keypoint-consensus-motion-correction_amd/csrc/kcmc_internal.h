@@ -87,6 +87,11 @@ int launch_match_filter(const int32_t* idx, const float* dist, const double* kp_
                         const int32_t* q_off, int n_frames, int n_tpl, double ratio, double d_lo, double d_hi,
                         double* kp_ordered, uint32_t* keep_bits, int32_t* counts, hipStream_t s);
 
+// The exact bilinear resize of kcmc_resize_u8 (resize.hip) without its argument checks:
+// the detector's pyramid builds its levels with it (orb.hip).  n_frames <= 65535.
+int launch_resize_u8(const uint8_t* src, int n_frames, int H, int W, uint8_t* dst, int dst_h, int dst_w,
+                     hipStream_t s);
+
 }  // namespace kcmc
 
 #define KCMC_TRY(expr)            \

@@ -28,6 +28,10 @@
 //                        largest key, ordered compaction of the kept candidates.
 // orb_describe_kernel    one wave per keypoint: moments (wave reduction), bin, 4 x 64
 //                        BRIEF comparisons of on-the-fly smoothed samples (ballots).
+//
+// kcmc_orb_detect_pyramid (opt-in, at the end of this file) runs the same kernels once per
+// level of a scale pyramid built by resize.hip and packs the levels' rows with
+// orb_pack_kernel; kcmc_orb_detect and its kernels are what they were without it.
 #include <cmath>
 
 #include "kcmc_internal.h"
@@ -480,6 +484,59 @@ __global__ __launch_bounds__(kThreads) void orb_describe_kernel(const uint8_t* _
   }
 }
 
+// The scale pyramid's levels as the pack kernel sees them (by value: 8 levels at most).
+constexpr int kMaxLevels = 8;
+struct PyrLevels {
+  const uint32_t* pos[kMaxLevels];  // [batch, quota] packed (y << 16 | x) in the level's pixels
+  const uint8_t* des[kMaxLevels];   // [batch, quota, 32]
+  int h[kMaxLevels], w[kMaxLevels], quota[kMaxLevels];
+};
+
+// Packs the levels' keypoints of one batch into the frame's rows, level 0 first and no
+// gaps: 32 lanes per output row (one descriptor byte each).  Lane 0 maps the position to
+// level 0 through the resize's own pixel map, one correctly rounded double division per
+// axis, x0 = ((2 x + 1) W - W_l) / (2 W_l) (level 0: exactly x), and writes the level.
+__global__ __launch_bounds__(kThreads) void orb_pack_kernel(PyrLevels lv, int n_levels,
+                                                            const int32_t* __restrict__ lvl_cnt, int batch,
+                                                            int n_features, int f_base, double* __restrict__ out_kp,
+                                                            uint8_t* __restrict__ out_des,
+                                                            uint8_t* __restrict__ out_level,
+                                                            int32_t* __restrict__ out_count) {
+  const int f = blockIdx.y;
+  const int k = blockIdx.x * (kThreads / 32) + (threadIdx.x >> 5), b = threadIdx.x & 31;
+  // the row's level: constant indices into the by-value struct (a per-thread index would
+  // send it through scratch)
+  int l = -1, off = 0;
+  size_t src = 0;
+  const uint32_t* pos = nullptr;
+  const uint8_t* des = nullptr;
+  long long Wl = 1, Hl = 1;
+#pragma unroll
+  for (int i = 0; i < kMaxLevels; ++i) {
+    if (i < n_levels) {
+      const int c = lvl_cnt[(size_t)i * batch + f];
+      if (k >= off && k < off + c) {
+        l = i;
+        src = (size_t)f * lv.quota[i] + (k - off);
+        pos = lv.pos[i], des = lv.des[i], Wl = lv.w[i], Hl = lv.h[i];
+      }
+      off += c;
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) out_count[f_base + f] = off;
+  if (l < 0 || k >= n_features) return;
+  const size_t o = (size_t)(f_base + f) * n_features + k;
+  out_des[o * 32 + b] = des[src * 32 + b];
+  if (b == 0) {
+    const uint32_t pp = pos[src];
+    const long long x = pp & 0xffffu, y = pp >> 16;
+    const long long W = lv.w[0], H = lv.h[0];
+    out_kp[2 * o] = (double)((2 * x + 1) * W - Wl) / (double)(2 * Wl);
+    out_kp[2 * o + 1] = (double)((2 * y + 1) * H - Hl) / (double)(2 * Hl);
+    out_level[o] = (uint8_t)l;
+  }
+}
+
 }  // namespace
 }  // namespace kcmc
 
@@ -533,6 +590,126 @@ extern "C" int kcmc_orb_detect(kcmc_ctx* ctx, const uint8_t* frames, int n_frame
     hipLaunchKernelGGL(orb_describe_kernel, dim3(ceil_div(n_features, kThreads / 64), nb), dim3(kThreads), 0, s, fr, H,
                        W, kpos, out_count, n_features, pattern, bin_cs, f0, words, out_des);
     rc = launch_check("orb kernels");
+  }
+  const int rc2 = workspace_free(ctx, ws, s);
+  return rc != KCMC_OK ? rc : rc2;
+}
+
+// The scale pyramid: level l is the exact bilinear resize (resize.hip) of
+// level l - 1; every level runs the kernels above unchanged on its image with its quota as
+// the budget, into per-level rows of the workspace, and orb_pack_kernel packs the levels
+// into the outputs.  The host gives every size and quota as integers.
+extern "C" int kcmc_orb_detect_pyramid(kcmc_ctx* ctx, const uint8_t* frames, int n_frames, int H, int W, int threshold,
+                                       int n_features, double harris_k, int edge, const int8_t* pattern,
+                                       const double* bin_cs, int n_levels, const int32_t* level_h,
+                                       const int32_t* level_w, const int32_t* level_quota, double* out_kp,
+                                       uint8_t* out_des, uint8_t* out_level, int32_t* out_count,
+                                       kcmc_stream_t stream) {
+  if (!ctx) return fail(KCMC_EINVAL, "kcmc_orb_detect_pyramid: ctx is NULL");
+  if (n_frames < 0 || H < 0 || W < 0 || n_features < 0)
+    return fail(KCMC_EINVAL, "kcmc_orb_detect_pyramid: negative size");
+  if (n_levels < 1 || n_levels > kMaxLevels) return fail(KCMC_EINVAL, "kcmc_orb_detect_pyramid: n_levels must be in [1, 8]");
+  if (!level_h || !level_w || !level_quota) return fail(KCMC_EINVAL, "kcmc_orb_detect_pyramid: NULL level array");
+  if (level_h[0] != H || level_w[0] != W)
+    return fail(KCMC_EINVAL, "kcmc_orb_detect_pyramid: level 0 must have the frames' size");
+  long long quota_sum = 0;
+  for (int l = 0; l < n_levels; ++l) {
+    if (level_h[l] < 1 || level_w[l] < 1 || (l > 0 && (level_h[l] > level_h[l - 1] || level_w[l] > level_w[l - 1])))
+      return fail(KCMC_EINVAL, "kcmc_orb_detect_pyramid: level sizes must be >= 1 and non-increasing");
+    if (level_quota[l] < 0) return fail(KCMC_EINVAL, "kcmc_orb_detect_pyramid: negative level quota");
+    quota_sum += level_quota[l];
+  }
+  if (quota_sum != n_features)
+    return fail(KCMC_EINVAL, "kcmc_orb_detect_pyramid: the level quotas must sum to n_features");
+  if (n_frames == 0) return KCMC_OK;
+  if (!frames || !out_count || (n_features > 0 && (!pattern || !bin_cs || !out_kp || !out_des || !out_level)))
+    return fail(KCMC_EINVAL, "kcmc_orb_detect_pyramid: NULL pointer");
+  if (edge < 16)
+    return fail(KCMC_EINVAL, "kcmc_orb_detect_pyramid: edge must be >= 16 (orientation disc + BRIEF patch)");
+  if (H > 65535 || W > 65535) return fail(KCMC_EUNSUPPORTED, "kcmc_orb_detect_pyramid: H, W must be < 65536");
+  if (threshold < 0 || threshold > 255)
+    return fail(KCMC_EINVAL, "kcmc_orb_detect_pyramid: threshold must be in [0, 255]");
+  hipStream_t s = (hipStream_t)stream;
+  // the levels that detect (a level too small for the margin, or without quota, yields nothing)
+  bool active[kMaxLevels];
+  int last = -1;
+  for (int l = 0; l < n_levels; ++l) {
+    active[l] = level_quota[l] > 0 && level_h[l] >= 2 * edge + 1 && level_w[l] >= 2 * edge + 1;
+    if (active[l]) last = l;
+  }
+  if (last < 0) return hip_check(hipMemsetAsync(out_count, 0, (size_t)n_frames * sizeof(int32_t), s), "hipMemsetAsync");
+  // Frames go in batches so that the workspace stays bounded: the candidate slots of level 0
+  // (reused by the smaller levels), the images of the levels 1 .. last, and the levels' rows.
+  const size_t tiles0 = (size_t)ceil_div(W, kTW) * ceil_div(H, kTH), slots0 = tiles0 * kSlots;
+  size_t level_px = 0;
+  for (int l = 1; l <= last; ++l) level_px += (size_t)level_h[l] * level_w[l];
+  const size_t per_frame = 2 * slots0 * (sizeof(uint64_t) + sizeof(uint32_t)) + tiles0 * 2 * sizeof(int32_t) + 4 +
+                           level_px + (size_t)n_features * (2 * sizeof(double) + sizeof(uint32_t) + 32) +
+                           kMaxLevels * sizeof(int32_t);
+  int batch = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_frames, ((size_t)1 << 30) / per_frame));
+  batch = std::min(batch, 65535);
+  void* ws = nullptr;
+  KCMC_TRY(workspace_alloc(ctx, &ws, per_frame * batch + 16 * (8 + 4 * kMaxLevels), s));
+  // 16-byte aligned pieces of the workspace
+  uint8_t* cur = static_cast<uint8_t*>(ws);
+  auto take = [&cur](size_t bytes) {
+    uint8_t* p = cur;
+    cur += (bytes + 15) & ~(size_t)15;
+    return p;
+  };
+  uint64_t* ckey = reinterpret_cast<uint64_t*>(take(batch * slots0 * sizeof(uint64_t)));
+  uint64_t* lkey = reinterpret_cast<uint64_t*>(take(batch * slots0 * sizeof(uint64_t)));
+  uint32_t* cpos = reinterpret_cast<uint32_t*>(take(batch * slots0 * sizeof(uint32_t)));
+  uint32_t* lpos = reinterpret_cast<uint32_t*>(take(batch * slots0 * sizeof(uint32_t)));
+  int32_t* ccnt = reinterpret_cast<int32_t*>(take(batch * tiles0 * sizeof(int32_t)));
+  int32_t* toff = reinterpret_cast<int32_t*>(take(batch * tiles0 * sizeof(int32_t)));
+  int32_t* ctot = reinterpret_cast<int32_t*>(take(batch * sizeof(int32_t)));
+  int32_t* lcnt = reinterpret_cast<int32_t*>(take((size_t)kMaxLevels * batch * sizeof(int32_t)));
+  PyrLevels lv = {};
+  double* lkp[kMaxLevels] = {};
+  uint8_t* ldes[kMaxLevels] = {};
+  uint32_t* lkpos[kMaxLevels] = {};
+  uint8_t* limg[kMaxLevels] = {};
+  for (int l = 0; l < n_levels; ++l) {
+    lv.h[l] = level_h[l], lv.w[l] = level_w[l], lv.quota[l] = level_quota[l];
+    if (active[l]) {
+      lkp[l] = reinterpret_cast<double*>(take((size_t)batch * level_quota[l] * 2 * sizeof(double)));
+      lkpos[l] = reinterpret_cast<uint32_t*>(take((size_t)batch * level_quota[l] * sizeof(uint32_t)));
+      ldes[l] = take((size_t)batch * level_quota[l] * 32);
+    }
+    if (l >= 1 && l <= last) limg[l] = take((size_t)batch * level_h[l] * level_w[l]);
+    lv.pos[l] = lkpos[l], lv.des[l] = ldes[l];
+  }
+  int rc = KCMC_OK;
+  for (int f0 = 0; f0 < n_frames && rc == KCMC_OK; f0 += batch) {
+    const int nb = std::min(batch, n_frames - f0);
+    rc = hip_check(hipMemsetAsync(lcnt, 0, (size_t)kMaxLevels * batch * sizeof(int32_t), s), "hipMemsetAsync");
+    const uint8_t* img = frames + (size_t)f0 * H * W;
+    for (int l = 0; l <= last && rc == KCMC_OK; ++l) {
+      const int h = level_h[l], w = level_w[l], q = level_quota[l];
+      if (l > 0) {
+        rc = launch_resize_u8(img, nb, level_h[l - 1], level_w[l - 1], limg[l], h, w, s);
+        img = limg[l];
+        if (rc != KCMC_OK) break;
+      }
+      if (!active[l]) continue;
+      const int ntx = ceil_div(w, kTW), nty = ceil_div(h, kTH), ntiles = ntx * nty;
+      const int words = (w & 3) == 0 && ((uintptr_t)img & 3) == 0;
+      hipLaunchKernelGGL(orb_candidates_kernel, dim3(ntx, ceil_div(nty, kSub), nb), dim3(kThreads), 0, s, img, h, w, words,
+                         threshold, harris_k, edge, ckey, cpos, ccnt);
+      hipLaunchKernelGGL(orb_offsets_kernel, dim3(nb), dim3(kThreads), 0, s, ccnt, ntiles, toff, ctot);
+      hipLaunchKernelGGL(orb_gather_kernel, dim3(ceil_div(ntiles, 4 * 8), nb), dim3(kThreads), 0, s, ckey, cpos, ccnt, toff,
+                         ntiles, lkey, lpos);
+      hipLaunchKernelGGL(orb_select_kernel, dim3(nb), dim3(kThreads), 0, s, lkey, lpos, ctot, ntiles, q, lkp[l], lkpos[l],
+                         lcnt + (size_t)l * batch, 0);
+      hipLaunchKernelGGL(orb_describe_kernel, dim3(ceil_div(q, kThreads / 64), nb), dim3(kThreads), 0, s, img, h, w,
+                         lkpos[l], lcnt + (size_t)l * batch, q, pattern, bin_cs, 0, words, ldes[l]);
+      rc = launch_check("orb pyramid kernels");
+    }
+    if (rc != KCMC_OK) break;
+    hipLaunchKernelGGL(orb_pack_kernel, dim3(ceil_div(n_features, kThreads / 32), nb), dim3(kThreads), 0, s, lv, n_levels,
+                       lcnt, batch, n_features, f0, out_kp, out_des, out_level, out_count);
+    rc = launch_check("orb_pack_kernel");
   }
   const int rc2 = workspace_free(ctx, ws, s);
   return rc != KCMC_OK ? rc : rc2;

@@ -824,19 +824,44 @@ def pyr_down_u8(frames_u8: torch.Tensor, dstsize=None, out: Optional[torch.Tenso
 
 
 # ------------------------------------------------------------ f1: detection
+def resize_u8(frames_u8: torch.Tensor, dst_h: int, dst_w: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The detector pyramid's exact bilinear resize (csrc/resize.hip, semantics in
+    include/kcmc.h) of every frame of a uint8 stack [F, H, W] to [F, dst_h, dst_w]; any
+    sizes in [1, 65535], upscaling included, no alignment requirement."""
+    dev = _device_of(frames_u8)
+    _require(frames_u8, "frames_u8", torch.uint8, dev)
+    if frames_u8.dim() != 3:
+        raise ValueError("frames_u8 must be [F, H, W]")
+    F, H, W = frames_u8.shape
+    dst_h, dst_w = int(dst_h), int(dst_w)
+    if out is None:
+        out = torch.empty((F, max(dst_h, 0), max(dst_w, 0)), dtype=torch.uint8, device=dev)
+    else:
+        _require(out, "out", torch.uint8, dev)
+        if tuple(out.shape) != (F, dst_h, dst_w):
+            raise ValueError("out must be [F, dst_h, dst_w]")
+    _lib.check(_lib.load().kcmc_resize_u8(_ctx(dev).handle, _ptr(frames_u8), F, H, W, _ptr(out), dst_h, dst_w,
+                                          _stream(dev)))
+    return out
+
+
 @dataclass
 class Keypoints:
     kp: torch.Tensor      # [F, n_features, 2] f64 (x, y); rows >= count[f] undefined
     des: torch.Tensor     # [F, n_features, 32] u8
     count: torch.Tensor   # [F] i32
+    level: Optional[torch.Tensor] = None  # [F, n_features] u8, the pyramid path only (n_levels > 1)
 
 
 def detect_orb(frames_u8: torch.Tensor, params=None) -> Keypoints:
     """The build's ORB-style detector (csrc/orb.hip) for every frame of a uint8 stack:
-    replaces detector.detectAndCompute (VA:114-116, VA:190-192) on the device."""
+    replaces detector.detectAndCompute (VA:114-116, VA:190-192) on the device.
+    params.n_levels > 1 detects on the scale pyramid (kcmc_orb_detect_pyramid: coordinates
+    in level-0 pixels, Keypoints.level set); n_levels == 1 is the single-scale entry."""
     from . import orb
 
     params = params or orb.OrbParams()
+    orb._check_pyramid(params.n_levels, params.scale_factor)
     dev = _device_of(frames_u8)
     _require(frames_u8, "frames_u8", torch.uint8, dev)
     if frames_u8.dim() == 2:
@@ -850,6 +875,18 @@ def detect_orb(frames_u8: torch.Tensor, params=None) -> Keypoints:
                     count=torch.empty((F,), dtype=torch.int32, device=dev))
     pattern = torch.from_numpy(orb.rotated_patterns()).to(dev)
     cs = torch.from_numpy(orb.bin_edges()).to(dev)
+    L = int(params.n_levels)
+    if L > 1:
+        sizes = orb.level_sizes(H, W, L, params.scale_factor)
+        lh = np.array([max(h, 1) for h, _ in sizes], np.int32)  # a 1-px axis cannot detect anyway
+        lw = np.array([max(w, 1) for _, w in sizes], np.int32)
+        quota = np.array(orb.level_quotas(N, L, params.scale_factor), np.int32)
+        res.level = torch.empty((F, N), dtype=torch.uint8, device=dev)
+        _lib.check(_lib.load().kcmc_orb_detect_pyramid(
+            _ctx(dev).handle, _ptr(frames_u8), F, H, W, int(params.fast_threshold), N, float(params.harris_k),
+            int(params.edge), _ptr(pattern), _ptr(cs), L, _np_ptr(lh), _np_ptr(lw), _np_ptr(quota), _ptr(res.kp),
+            _ptr(res.des), _ptr(res.level), _ptr(res.count), _stream(dev)))
+        return res
     _lib.check(_lib.load().kcmc_orb_detect(
         _ctx(dev).handle, _ptr(frames_u8), F, H, W, int(params.fast_threshold), N, float(params.harris_k),
         int(params.edge), _ptr(pattern), _ptr(cs), _ptr(res.kp), _ptr(res.des), _ptr(res.count), _stream(dev)))

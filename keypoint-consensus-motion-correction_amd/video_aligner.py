@@ -82,6 +82,14 @@ class GpuOrbDetector:
         return [_CvKeyPoint(float(x), float(y)) for x, y in kp], k.des[0, :n].cpu().numpy()
 
 
+def _gpu_orb_multiscale() -> GpuOrbDetector:
+    """The same detector on an 8-level scale pyramid of ratio 1.2: keeps
+    matching under the magnification changes the similarity model is there for."""
+    from . import orb
+
+    return GpuOrbDetector(orb.OrbParams(n_levels=8))
+
+
 def _as_numpy(x) -> np.ndarray:
     return x.cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
 
@@ -97,6 +105,8 @@ class VideoAligner:
         "brisk": _cv2_factory("BRISK_create"),
         # New: the build's exact ORB-style detector on the GPU (no OpenCV needed).
         "orb": GpuOrbDetector,
+        # New: the same on a scale pyramid (8 levels, ratio 1.2), for zoom drift / focus breathing.
+        "orb_ms": _gpu_orb_multiscale,
     }
     N_KP_GLOBAL_MIN = 5
     N_KP_FRAME_SKIP = 3
