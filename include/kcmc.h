@@ -25,6 +25,9 @@
  *   kcmc_stack_sum_u16 / kcmc_frame_stats_u16  <- nothing in the reference (an extension):
  *                             the mean image of the aligned stack and every frame's
  *                             correlation moments with it.
+ *   kcmc_shift_search_u16  <- nothing in the reference (an extension): the same moments at
+ *                             every integer shift in a window, for the intensity fallback
+ *                             of frames without a model.
  *
  * Conventions
  *   - Plain pointers and sizes only.  Pointers named *_dev are device (HBM) pointers
@@ -461,6 +464,34 @@ int kcmc_stack_sum_u16(kcmc_ctx* ctx, const uint16_t* frames_dev, int n_frames, 
 int kcmc_frame_stats_u16(kcmc_ctx* ctx, const uint16_t* frames_dev, int n_frames, int H, int W,
                          const uint16_t* ref_dev, int y0, int y1, int x0, int x1, long long* out_dev,
                          kcmc_stream_t stream);
+
+/* ------------------------------------- s1: exact shift search (intensity fallback)
+ * Build-defined: the reference never registers a frame RANSAC gave no model (it
+ * interpolates the frame's map from its neighbours, VA:347-437) and has no intensity mode.
+ *
+ * out_dev [n_sel, 2R + 1, 2R + 1, 5] i64: entry [s][dy + R][dx + R] = (sum a, sum b, sum a^2,
+ * sum b^2, sum a*b) over rows [y0, y1) and columns [x0, x1), with
+ *   a = frames_dev[frame_idx_dev[s]][y + dy][x + dx]   (frames_dev [n_frames, H, W] u16),
+ *   b = ref_dev[y][x]                                  (ref_dev [H, W] u16),
+ * i.e. the moments of kcmc_frame_stats_u16 (same layout and meaning) at every integer shift
+ * of the frame in [-R, R]^2; entry (0, 0) equals that function's row for the same frame and
+ * rectangle.  A shift (dy, dx) with a high correlation says frame(p + d) ~ ref(p).
+ *
+ * frame_idx_dev [n_sel] i32; NULL = frames 0 .. n_sel - 1.  An index outside [0, n_frames)
+ * gives an all-zero row and is never read through; repeated and unordered indices are fine.
+ *
+ * Contract (KCMC_EINVAL before any device work otherwise, as for a NULL ctx or pointer):
+ * 1 <= R <= 16, y0 < y1, x0 < x1, y0 - R >= 0, y1 + R <= H, x0 - R >= 0, x1 + R <= W,
+ * H * W < 2^31, out_dev 8-byte aligned.  n_sel == 0 is KCMC_OK.  Any alignment of frames_dev /
+ * ref_dev and any W: the 16-byte path needs W % 8 == 0 and 16-byte aligned frames_dev and
+ * ref_dev, everything else is staged element by element.
+ *
+ * Exact: every sum is a 64-bit integer (no floating point, no dependence on the order in
+ * which workgroups finish; narrower partial sums are bounded for all-65535 input).
+ * Asynchronous on `stream`, no allocation; zeroes its own output first. */
+int kcmc_shift_search_u16(kcmc_ctx* ctx, const uint16_t* frames_dev, int n_frames, int H, int W,
+                          const int32_t* frame_idx_dev, int n_sel, const uint16_t* ref_dev, int y0, int y1,
+                          int x0, int x1, int R, long long* out_dev, kcmc_stream_t stream);
 
 #ifdef __cplusplus
 }

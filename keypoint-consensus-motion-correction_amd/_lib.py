@@ -60,6 +60,7 @@ EXPORTED_SYMBOLS = (
     "kcmc_pyr_down_u8",
     "kcmc_stack_sum_u16",
     "kcmc_frame_stats_u16",
+    "kcmc_shift_search_u16",
 )
 
 KCMC_MODEL_EUCLIDEAN = 0
@@ -130,6 +131,7 @@ _SIGNATURES = {
     "kcmc_pyr_down_u8": ([P, P, I, I, I, P, I, I, P], I),
     "kcmc_stack_sum_u16": ([P, P, I, ctypes.c_ulonglong, P, P, P], I),
     "kcmc_frame_stats_u16": ([P, P, I, I, I, P, I, I, I, I, P, P], I),
+    "kcmc_shift_search_u16": ([P, P, I, I, I, P, I, P, I, I, I, I, I, P, P], I),
 }
 
 

@@ -30,6 +30,7 @@ import numpy as np
 import torch
 
 from . import affines as _aff
+from . import fallback as _fb
 from . import multidevice as _md
 from . import piecewise as _pw
 from . import pipeline as _pl
@@ -164,6 +165,21 @@ class VideoAligner:
     PIECEWISE_WINDOW = 1.0
     PIECEWISE_MIN_POINTS = 6
     PIECEWISE_MAX_RESIDUAL = 8.0
+    # New (opt-in, kcmc_amd.fallback; build-defined, the reference has no such mode): what
+    # happens to the sample frames RANSAC gave no model (skipped_idxs).  "interpolate": the
+    # reference's behaviour, their maps are interpolated from their neighbours.  "correlation":
+    # after that, each of them is searched against the mean image of the registered sample
+    # frames at every integer shift within FALLBACK_RADIUS px (exact Pearson correlation over
+    # the valid region shrunk by the radius, csrc/shift_search.hip); a peak above
+    # FALLBACK_MIN_CORRELATION that is not on the window's border -- refined by a parabola per
+    # axis with FALLBACK_SUBPIXEL -- corrects the frame's map, and the frame is warped again
+    # from its source.  Only frames in skipped_idxs are touched; skipped_idxs and
+    # interpolated_idxs stay what they are.  Results: fallback_shifts, fallback_correlations,
+    # fallback_idxs.  Grayscale stacks, 2 x 3 models, not with PIECEWISE_GRID.
+    FALLBACK = "interpolate"
+    FALLBACK_RADIUS = 8             # 1..16 px
+    FALLBACK_MIN_CORRELATION = 0.0  # r <= this: no resemblance, keep the interpolated map
+    FALLBACK_SUBPIXEL = True
 
     def __init__(self, logger: LoggerAdapter = None):
         self.logger = logger
@@ -177,6 +193,7 @@ class VideoAligner:
         self._logged_one_device = False
         self._reset_quality()
         self._reset_piecewise()
+        self._reset_fallback()
 
     # ------------------------------------------------------------------ helpers
     @classmethod
@@ -257,6 +274,47 @@ class VideoAligner:
         self.patch_fitted = ex.get("patch_fitted")
         if self.patch_residuals is not None:  # the maps the field was added to
             self.affines = res.affines
+
+    # ------------------------------------------- intensity fallback for frames without a model
+    def _reset_fallback(self) -> None:
+        self.fallback_shifts = None
+        self.fallback_correlations = None
+        self.fallback_idxs = None
+
+    def _fallback_on(self, images=None) -> bool:
+        """Whether the correlation fallback runs, after the checks that must fail before any
+        work (``images``: only its number of dimensions is read, when it has one)."""
+        if self.FALLBACK == "interpolate":
+            return False
+        if self.FALLBACK != "correlation":
+            raise ValueError(f"FALLBACK must be 'interpolate' or 'correlation', got {self.FALLBACK!r}")
+        _fb.check_radius(self.FALLBACK_RADIUS)
+        if self.RANSAC_MODEL == "projective":
+            raise NotImplementedError("FALLBACK = 'correlation' does not support RANSAC_MODEL = 'projective' (the "
+                                      "shift is composed with a 2 x 3 map)")
+        if self.PIECEWISE_GRID is not None:
+            raise NotImplementedError("FALLBACK = 'correlation' does not run together with PIECEWISE_GRID")
+        if getattr(images, "ndim", 3) != 3:
+            raise NotImplementedError("FALLBACK = 'correlation' supports grayscale stacks [F, H, W] only")
+        return True
+
+    def _with_fallback(self, hot: Callable, slabs: Sequence[_pl.SlabInputs], n_images: int, rate: int) -> Callable:
+        """``hot`` itself with the switch off; with it on, ``hot`` followed by the fallback pass
+        over its result, so that every pass of _run_passes carries the correction."""
+        if not self._fallback_on():
+            return hot
+
+        def corrected():
+            res = hot()
+            fb = _fb.correct_skipped(res, [inp.frames for inp in slabs], n_images, rate, self.RANSAC_MODEL,
+                                     int(self.FALLBACK_RADIUS), float(self.FALLBACK_MIN_CORRELATION),
+                                     bool(self.FALLBACK_SUBPIXEL), logger=self.logger)
+            self.fallback_shifts, self.fallback_correlations = fb.shifts, fb.correlations
+            self.fallback_idxs = fb.idxs
+            self.affines = res.affines
+            return res
+
+        return corrected
 
     # ------------------------------------------------- quality metrics, template refinement
     def _reset_quality(self) -> None:
@@ -362,6 +420,8 @@ class VideoAligner:
         self._quality_on()
         self._reset_piecewise()
         self._piecewise_on(images)
+        self._reset_fallback()
+        self._fallback_on(images)
         self._log_one_device()
         self.logger.info(f"aligning {len(images)} frames with n_kp_global: {n_kp_global} and {detector_algorithm}")
         if not 0 <= self.TEMPLATE_FRAME_LOC <= 1:
@@ -528,8 +588,10 @@ class VideoAligner:
         self.logger.info("generating keypoint consensus...")
         t_start = time.time()
         # the metrics read the aligned slabs where they are, before they are gathered
-        res = self._run_passes(lambda: _md.align_split(slabs, ranges, cfg, logger=self.logger), slabs, ranges[-1].f1,
-                               int(cfg.frame_downsample_rate), detect_template)
+        n_images, rate = ranges[-1].f1, int(cfg.frame_downsample_rate)
+        hot = self._with_fallback(lambda: _md.align_split(slabs, ranges, cfg, logger=self.logger), slabs, n_images,
+                                  rate)
+        res = self._run_passes(hot, slabs, n_images, rate, detect_template)
         self.interpolated_idxs = res.interpolated
         self.logger.info(f"aligned frames in: {round(time.time() - t_start)} s")
         aligned = _md.gather_aligned(res, out_device)
@@ -564,6 +626,8 @@ class VideoAligner:
         self._quality_on(refine_supported=False)
         self._reset_piecewise()
         self._piecewise_on(images)
+        self._reset_fallback()
+        self._fallback_on(images)
         self._log_one_device()
         self._kp_template = np.asarray(kp_template, dtype=np.float64).reshape(-1, 2)
         self._des_template = np.asarray(des_template, dtype=np.uint8)
@@ -599,8 +663,9 @@ class VideoAligner:
         cfg = self._config(n_kp_global, rate)
         self.logger.info("generating keypoint consensus...")
         t_start = time.time()
-        res = self._run_passes(lambda: _pl.align_slab(inp, cfg, logger=self.logger), [inp], inp.frames.shape[0], rate,
-                               detect_template)
+        n_images = inp.frames.shape[0]
+        hot = self._with_fallback(lambda: _pl.align_slab(inp, cfg, logger=self.logger), [inp], n_images, rate)
+        res = self._run_passes(hot, [inp], n_images, rate, detect_template)
         self.interpolated_idxs = res.interpolated
         self.logger.info(f"aligned frames in: {round(time.time() - t_start)} s")
         self._take_piecewise(res)
