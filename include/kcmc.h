@@ -28,6 +28,9 @@
  *   kcmc_shift_search_u16  <- nothing in the reference (an extension): the same moments at
  *                             every integer shift in a window, for the intensity fallback
  *                             of frames without a model.
+ *   kcmc_gradient_sums_u16 <- nothing in the reference (an extension): the right-hand side
+ *                             of one least-squares step of every frame against the mean
+ *                             image, for the intensity refinement of the frames' maps.
  *
  * Conventions
  *   - Plain pointers and sizes only.  Pointers named *_dev are device (HBM) pointers
@@ -492,6 +495,50 @@ int kcmc_frame_stats_u16(kcmc_ctx* ctx, const uint16_t* frames_dev, int n_frames
 int kcmc_shift_search_u16(kcmc_ctx* ctx, const uint16_t* frames_dev, int n_frames, int H, int W,
                           const int32_t* frame_idx_dev, int n_sel, const uint16_t* ref_dev, int y0, int y1,
                           int x0, int x1, int R, long long* out_dev, kcmc_stream_t stream);
+
+/* ----------------------------- g1: gradient sums (intensity refinement of the maps)
+ * Build-defined: the reference registers frames on keypoints only and has no dense step.
+ *
+ * One linearised least-squares (Gauss-Newton) step of an aligned frame a against a
+ * reference image b models a(p) ~ alpha b(p - u(p)) + beta, u(p) = (tx - theta y', ty + theta x'),
+ * as a ~ alpha b + beta + qx gx + qy gy + qt gr with the integer gradients (twice the central
+ * difference)
+ *   gx(y, x) = b(y, x + 1) - b(y, x - 1),   gy(y, x) = b(y + 1, x) - b(y - 1, x),
+ *   gr = x' gy - y' gx,   x' = x - (x0 + x1) / 2,   y' = y - (y0 + y1) / 2   (integer division),
+ * and tx = -2 qx / alpha, ty = -2 qy / alpha, theta = -2 qt / alpha.  The normal matrix depends on
+ * b and the rectangle only (host, kcmc_amd.refine.gram); this entry point gives what
+ * depends on the frame.
+ *
+ * out_dev [n_sel, n_bands, 7] i64, n_bands = ceil((y1 - y0) / band_rows): row [s][k] = (sum a,
+ * sum a^2, sum a b, sum a gx, sum a gy, sum x' a gy, sum y' a gx) over the rows [y0 + k band_rows,
+ * min(y1, y0 + (k + 1) band_rows)) and the columns [x0, x1), a = frames_dev[frame_idx_dev[s]]
+ * (frames_dev [n_frames, H, W] u16), b = ref_dev [H, W] u16.  The caller adds the bands (the
+ * sum over bands may pass 2^63).  sum a gr = sum x' a gy - sum y' a gx.  Pixels outside the
+ * rectangle contribute nothing as a; as b they are read where the gradient at the
+ * rectangle's edge needs them.
+ *
+ * frame_idx_dev [n_sel] i32; NULL = frames 0 .. n_sel - 1.  An index outside [0, n_frames)
+ * gives all-zero rows and is never read through; repeated and unordered indices are fine.
+ *
+ * Contract (KCMC_EINVAL before any device work otherwise, as for a NULL ctx or pointer):
+ * 1 <= y0 < y1 <= H - 1 and 1 <= x0 < x1 <= W - 1 (the gradient reads +-1), H * W < 2^31,
+ * out_dev 8-byte aligned, band_rows >= 1 and
+ *   band_rows * (x1 - x0) * max(x1 - x0, y1 - y0) < 2^32.
+ * That bound keeps every band sum below 2^63 for any input: a band has at most
+ * band_rows * (x1 - x0) pixels, a <= 65535 and |gx|, |gy| <= 65535 make every product a^2, a b,
+ * a g smaller than 2^32, and |x'| <= (x1 - x0) / 2, |y'| <= (y1 - y0) / 2, so the largest sum is
+ * below band_rows * (x1 - x0) * (max / 2) * 2^32 < 2^63.  (1080p: one band would do; 4K needs
+ * several.)  n_sel == 0 is KCMC_OK; KCMC_EUNSUPPORTED when n_sel * n_bands >= 2^31.  Any
+ * alignment of frames_dev / ref_dev and any W: the 16-byte path needs W % 8 == 0 and 16-byte
+ * aligned frames_dev and ref_dev, everything else is read element by element.
+ *
+ * Exact: every value is a signed 64-bit integer (no floating point); one workgroup owns
+ * each (frame, band) and writes its row with plain stores, so nothing depends on the order
+ * in which workgroups finish.  Asynchronous on `stream`, no allocation, no memset: every
+ * row of out_dev is written. */
+int kcmc_gradient_sums_u16(kcmc_ctx* ctx, const uint16_t* frames_dev, int n_frames, int H, int W,
+                           const int32_t* frame_idx_dev, int n_sel, const uint16_t* ref_dev, int y0, int y1,
+                           int x0, int x1, int band_rows, long long* out_dev, kcmc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -9,9 +9,9 @@ include/kcmc.h); the host keeps the reference's Python API.
 Import as ``import kcmc_amd`` (the repository-root shim ``kcmc_amd.py`` maps that
 name onto this directory).
 """
-from . import fallback, piecewise, quality
+from . import fallback, piecewise, quality, refine
 from .affines import AlignmentError
 from .video_aligner import LoResVideoAligner, VideoAligner
 
-__all__ = ["VideoAligner", "LoResVideoAligner", "AlignmentError", "fallback", "piecewise", "quality"]
+__all__ = ["VideoAligner", "LoResVideoAligner", "AlignmentError", "fallback", "piecewise", "quality", "refine"]
 __version__ = "0.1.0"

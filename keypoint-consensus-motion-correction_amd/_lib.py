@@ -61,6 +61,7 @@ EXPORTED_SYMBOLS = (
     "kcmc_stack_sum_u16",
     "kcmc_frame_stats_u16",
     "kcmc_shift_search_u16",
+    "kcmc_gradient_sums_u16",
 )
 
 KCMC_MODEL_EUCLIDEAN = 0
@@ -132,6 +133,7 @@ _SIGNATURES = {
     "kcmc_stack_sum_u16": ([P, P, I, ctypes.c_ulonglong, P, P, P], I),
     "kcmc_frame_stats_u16": ([P, P, I, I, I, P, I, I, I, I, P, P], I),
     "kcmc_shift_search_u16": ([P, P, I, I, I, P, I, P, I, I, I, I, I, P, P], I),
+    "kcmc_gradient_sums_u16": ([P, P, I, I, I, P, I, P, I, I, I, I, I, P, P], I),
 }
 
 

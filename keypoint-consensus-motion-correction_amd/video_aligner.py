@@ -35,6 +35,7 @@ from . import multidevice as _md
 from . import piecewise as _pw
 from . import pipeline as _pl
 from . import quality as _q
+from . import refine as _rf
 from . import stages
 from .affines import AlignmentError
 
@@ -180,6 +181,21 @@ class VideoAligner:
     FALLBACK_RADIUS = 8             # 1..16 px
     FALLBACK_MIN_CORRELATION = 0.0  # r <= this: no resemblance, keep the interpolated map
     FALLBACK_SUBPIXEL = True
+    # New (opt-in, kcmc_amd.refine; build-defined, the reference has no such mode): the dense
+    # step after the keypoints.  "intensity": REFINE_ITERS times, every frame of the stack
+    # (sample or not, skipped or not) takes one linearised least-squares step against the mean
+    # image of the registered sample frames over the valid region -- gain, offset, translation
+    # and, with REFINE_MOTION = "rigid", a small rotation about the region's centre, from
+    # seven exact integer sums per frame (csrc/refine.hip); the step is limited to
+    # REFINE_MAX_STEP px at the region's corners, composed into the frame's map, the frame is
+    # warped again from its source, and the step is kept only where the frame's correlation
+    # with the mean image rose.  Runs after the fallback when both are on; skipped_idxs and
+    # interpolated_idxs stay what they are.  Results: refine_steps, refine_correlations,
+    # refine_idxs.  Grayscale stacks, 2 x 3 models, not with PIECEWISE_GRID.
+    REFINE = "none"
+    REFINE_ITERS = 2
+    REFINE_MOTION = "rigid"         # or "translation"
+    REFINE_MAX_STEP = 1.0           # px
 
     def __init__(self, logger: LoggerAdapter = None):
         self.logger = logger
@@ -194,6 +210,7 @@ class VideoAligner:
         self._reset_quality()
         self._reset_piecewise()
         self._reset_fallback()
+        self._reset_refine()
 
     # ------------------------------------------------------------------ helpers
     @classmethod
@@ -316,6 +333,49 @@ class VideoAligner:
 
         return corrected
 
+    # ------------------------------------------------ intensity refinement of every frame's map
+    def _reset_refine(self) -> None:
+        self.refine_steps = None
+        self.refine_correlations = None
+        self.refine_idxs = None
+
+    def _refine_on(self, images=None) -> bool:
+        """Whether the intensity refinement runs, after the checks that must fail before any
+        work (``images``: only its number of dimensions is read, when it has one)."""
+        if self.REFINE == "none":
+            return False
+        if self.REFINE != "intensity":
+            raise ValueError(f"REFINE must be 'none' or 'intensity', got {self.REFINE!r}")
+        try:
+            _rf.check_options(self.REFINE_ITERS, self.REFINE_MOTION, self.REFINE_MAX_STEP)
+        except ValueError as e:
+            raise ValueError(f"REFINE_ITERS / REFINE_MOTION / REFINE_MAX_STEP: {e}") from None
+        if self.RANSAC_MODEL == "projective":
+            raise NotImplementedError("REFINE = 'intensity' does not support RANSAC_MODEL = 'projective' (the "
+                                      "step is composed with a 2 x 3 map)")
+        if self.PIECEWISE_GRID is not None:
+            raise NotImplementedError("REFINE = 'intensity' does not run together with PIECEWISE_GRID")
+        if getattr(images, "ndim", 3) != 3:
+            raise NotImplementedError("REFINE = 'intensity' supports grayscale stacks [F, H, W] only")
+        return True
+
+    def _with_refine(self, hot: Callable, slabs: Sequence[_pl.SlabInputs], n_images: int, rate: int) -> Callable:
+        """``hot`` itself with the switch off; with it on, ``hot`` (the fallback included)
+        followed by the refinement pass over its result, in every pass of _run_passes."""
+        if not self._refine_on():
+            return hot
+
+        def refined():
+            res = hot()
+            rf = _rf.refine_frames(res, [inp.frames for inp in slabs], n_images, rate, self.RANSAC_MODEL,
+                                   int(self.REFINE_ITERS), self.REFINE_MOTION, float(self.REFINE_MAX_STEP),
+                                   logger=self.logger)
+            self.refine_steps, self.refine_correlations, self.refine_idxs = rf.steps, rf.correlations, rf.idxs
+            self.affines = res.affines
+            return res
+
+        return refined
+
     # ------------------------------------------------- quality metrics, template refinement
     def _reset_quality(self) -> None:
         self.frame_correlations = None
@@ -422,6 +482,8 @@ class VideoAligner:
         self._piecewise_on(images)
         self._reset_fallback()
         self._fallback_on(images)
+        self._reset_refine()
+        self._refine_on(images)
         self._log_one_device()
         self.logger.info(f"aligning {len(images)} frames with n_kp_global: {n_kp_global} and {detector_algorithm}")
         if not 0 <= self.TEMPLATE_FRAME_LOC <= 1:
@@ -591,6 +653,7 @@ class VideoAligner:
         n_images, rate = ranges[-1].f1, int(cfg.frame_downsample_rate)
         hot = self._with_fallback(lambda: _md.align_split(slabs, ranges, cfg, logger=self.logger), slabs, n_images,
                                   rate)
+        hot = self._with_refine(hot, slabs, n_images, rate)
         res = self._run_passes(hot, slabs, n_images, rate, detect_template)
         self.interpolated_idxs = res.interpolated
         self.logger.info(f"aligned frames in: {round(time.time() - t_start)} s")
@@ -628,6 +691,8 @@ class VideoAligner:
         self._piecewise_on(images)
         self._reset_fallback()
         self._fallback_on(images)
+        self._reset_refine()
+        self._refine_on(images)
         self._log_one_device()
         self._kp_template = np.asarray(kp_template, dtype=np.float64).reshape(-1, 2)
         self._des_template = np.asarray(des_template, dtype=np.uint8)
@@ -665,6 +730,7 @@ class VideoAligner:
         t_start = time.time()
         n_images = inp.frames.shape[0]
         hot = self._with_fallback(lambda: _pl.align_slab(inp, cfg, logger=self.logger), [inp], n_images, rate)
+        hot = self._with_refine(hot, [inp], n_images, rate)
         res = self._run_passes(hot, [inp], n_images, rate, detect_template)
         self.interpolated_idxs = res.interpolated
         self.logger.info(f"aligned frames in: {round(time.time() - t_start)} s")
