@@ -30,7 +30,7 @@
 // The vector kernels need frame rows that start on 16-byte boundaries (a 16-byte aligned
 // base, and n_px resp. W a multiple of 8); everything else -- odd sizes, a slab view that
 // starts mid-allocation -- takes the element-wise kernels of the same layout.
-#include "kcmc_internal.h"
+#include "u16_rows.h"
 
 namespace kcmc {
 namespace {
@@ -41,14 +41,7 @@ constexpr int kMaxChunk = 65536;    // 32-bit accumulators
 constexpr int kTargetBlocks = 2048; // 256 CUs x 8 resident workgroups
 
 __device__ __forceinline__ void add8(uint32_t* acc, const uint4& q) {
-  acc[0] += q.x & 0xffffu;
-  acc[1] += q.x >> 16;
-  acc[2] += q.y & 0xffffu;
-  acc[3] += q.y >> 16;
-  acc[4] += q.z & 0xffffu;
-  acc[5] += q.z >> 16;
-  acc[6] += q.w & 0xffffu;
-  acc[7] += q.w >> 16;
+  for_each_px(q, [&](int j, uint32_t px) { acc[j] += px; });
 }
 
 // n_px % 8 == 0, frames 16-byte aligned.  grid (ceil(n_px / 2048), chunks).
@@ -134,28 +127,11 @@ __device__ __forceinline__ void acc_px(Sums& s, uint32_t a, uint32_t b) {
   }
 }
 
-// Lanes of the vector at column c0 (a multiple of 8) outside [x0, x1) read as 0.
-__device__ __forceinline__ uint4 mask8(uint4 q, int c0, int x0, int x1) {
-  if (c0 >= x0 && c0 + 8 <= x1) return q;
-  uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int c = c0 + 2 * k;
-    const uint32_t lo = (c >= x0 && c < x1) ? 0xffffu : 0u;
-    const uint32_t hi = (c + 1 >= x0 && c + 1 < x1) ? 0xffff0000u : 0u;
-    w[k] &= lo | hi;
-  }
-  return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
 template <bool WITH_B>
 __device__ __forceinline__ void acc_vec(Sums& s, const uint4& a, const uint4& b) {
-  const uint32_t wa[4] = {a.x, a.y, a.z, a.w}, wb[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    acc_px<WITH_B>(s, wa[k] & 0xffffu, wb[k] & 0xffffu);
-    acc_px<WITH_B>(s, wa[k] >> 16, wb[k] >> 16);
-  }
+  uint32_t pb[8];
+  unpack8(b, pb);
+  for_each_px(a, [&](int j, uint32_t pa) { acc_px<WITH_B>(s, pa, pb[j]); });
 }
 
 // VEC: W % 8 == 0, frames and ref 16-byte aligned.  The items of a frame are the vectors
@@ -198,18 +174,12 @@ __device__ __forceinline__ void frame_sums(Sums& s, const uint16_t* __restrict__
   }
 }
 
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-  return v;
-}
-
 // grid (n_frames, workgroups per frame).  out [n_frames, 5] zeroed before the launch.
 template <bool VEC>
 __global__ __launch_bounds__(kThreads) void frame_stats_kernel(const uint16_t* __restrict__ frames, int H, int W,
                                                                const uint16_t* __restrict__ ref, int y0, int y1,
                                                                int x0, int x1, unsigned long long* __restrict__ out) {
-  __shared__ unsigned long long red[5][kThreads / 64];
+  __shared__ u64 red[5][kThreads / 64];
   const size_t f = blockIdx.x;
   const uint16_t* fr = frames + f * (size_t)H * W;
   Sums s;
@@ -217,32 +187,51 @@ __global__ __launch_bounds__(kThreads) void frame_stats_kernel(const uint16_t* _
     frame_sums<VEC, true>(s, fr, ref, W, y0, y1, x0, x1);
   else
     frame_sums<VEC, false>(s, fr, ref, W, y0, y1, x0, x1);
-  const unsigned long long v[5] = {wave_sum(s.a), wave_sum(s.b), wave_sum(s.aa), wave_sum(s.bb), wave_sum(s.ab)};
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0)
-    for (int k = 0; k < 5; ++k) red[k][wave] = v[k];
-  __syncthreads();
-  if (threadIdx.x < 5) {
-    const int k = threadIdx.x;
-    if (f == 0 || (k != 1 && k != 3)) {
-      unsigned long long t = 0;
-      for (int w = 0; w < kThreads / 64; ++w) t += red[k][w];
-      if (t) atomicAdd(&out[f * 5 + k], t);
-    }
-  }
+  const u64 v[5] = {s.a, s.b, s.aa, s.bb, s.ab};
+  const u64 t = block_sums(v, red);
+  const int k = threadIdx.x;
+  if (k < 5 && (f == 0 || (k != 1 && k != 3)) && t) atomicAdd(&out[f * 5 + k], t);
 }
 
-// Sb and Sbb of frame 0 to every other frame (runs after frame_stats_kernel on the stream).
-__global__ __launch_bounds__(kThreads) void frame_stats_copy_b_kernel(unsigned long long* __restrict__ out,
-                                                                      int n_frames) {
-  const size_t f = blockIdx.x * (size_t)kThreads + threadIdx.x + 1;
-  if (f < (size_t)n_frames) {
-    out[f * 5 + 1] = out[1];
-    out[f * 5 + 3] = out[3];
-  }
+// launch_copy_b (u16_rows.h): here the group is all frames, in shift_search.hip the shifts of one frame.
+__global__ __launch_bounds__(kThreads) void copy_b_kernel(u64* __restrict__ out, size_t n_entries, int group) {
+  const size_t i = blockIdx.x * (size_t)kThreads + threadIdx.x;
+  if (i >= n_entries) return;
+  const size_t first = i / group * group;
+  if (i == first) return;
+  out[i * 5 + 1] = out[first * 5 + 1];
+  out[i * 5 + 3] = out[first * 5 + 3];
 }
 
 }  // namespace
+
+int launch_copy_b(u64* out, size_t n_entries, int group, hipStream_t s) {
+  hipLaunchKernelGGL(copy_b_kernel, dim3((unsigned)((n_entries + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, out,
+                     n_entries, group);
+  return launch_check("copy_b_kernel");
+}
+
+int check_rect(const char* fn, kcmc_ctx* ctx, int n_frames, int n_sel, int H, int W, int y0, int y1, int x0, int x1,
+               int margin, const char* grown) {
+  const std::string p = std::string(fn) + ": ";
+  if (!ctx) return fail(KCMC_EINVAL, p + "ctx is NULL");
+  if (n_frames < 0 || n_sel < 0 || H <= 0 || W <= 0) return fail(KCMC_EINVAL, p + "bad shape");
+  if ((long long)H * W >= (1ll << 31)) return fail(KCMC_EINVAL, p + "H * W must be < 2^31");
+  if (y0 >= y1 || x0 >= x1) return fail(KCMC_EINVAL, p + "empty rectangle");
+  const long long m = margin;
+  if (y0 < m || x0 < m || y1 + m > H || x1 + m > W)
+    return fail(KCMC_EINVAL, p + (grown ? "the rectangle grown by " + std::string(grown) + " leaves the image"
+                                        : std::string("rectangle outside the image")));
+  return KCMC_OK;
+}
+
+int check_pointers(const char* fn, const void* frames, int n_frames, const void* ref, const void* out) {
+  const std::string p = std::string(fn) + ": ";
+  if (!ref || !out || (n_frames > 0 && !frames)) return fail(KCMC_EINVAL, p + "NULL pointer");
+  if (((uintptr_t)out & 7) != 0) return fail(KCMC_EINVAL, p + "out must be 8-byte aligned");
+  return KCMC_OK;
+}
+
 }  // namespace kcmc
 
 using namespace kcmc;
@@ -289,17 +278,12 @@ extern "C" int kcmc_stack_sum_u16(kcmc_ctx* ctx, const uint16_t* frames, int n_f
 extern "C" int kcmc_frame_stats_u16(kcmc_ctx* ctx, const uint16_t* frames, int n_frames, int H, int W,
                                     const uint16_t* ref, int y0, int y1, int x0, int x1, long long* out,
                                     kcmc_stream_t stream) {
-  if (!ctx) return fail(KCMC_EINVAL, "kcmc_frame_stats_u16: ctx is NULL");
-  if (n_frames < 0 || H <= 0 || W <= 0) return fail(KCMC_EINVAL, "kcmc_frame_stats_u16: bad shape");
-  if ((long long)H * W >= (1ll << 31)) return fail(KCMC_EINVAL, "kcmc_frame_stats_u16: H * W must be < 2^31");
-  if (y0 < 0 || y1 > H || x0 < 0 || x1 > W) return fail(KCMC_EINVAL, "kcmc_frame_stats_u16: rectangle outside the image");
-  if (y0 >= y1 || x0 >= x1) return fail(KCMC_EINVAL, "kcmc_frame_stats_u16: empty rectangle");
+  KCMC_TRY(check_rect("kcmc_frame_stats_u16", ctx, n_frames, n_frames, H, W, y0, y1, x0, x1, 0, nullptr));
   if (n_frames == 0) return KCMC_OK;
-  if (!frames || !ref || !out) return fail(KCMC_EINVAL, "kcmc_frame_stats_u16: NULL pointer");
-  if (((uintptr_t)out & 7) != 0) return fail(KCMC_EINVAL, "kcmc_frame_stats_u16: out must be 8-byte aligned");
+  KCMC_TRY(check_pointers("kcmc_frame_stats_u16", frames, n_frames, ref, out));
   hipStream_t s = (hipStream_t)stream;
   KCMC_TRY(hip_check(hipMemsetAsync(out, 0, (size_t)n_frames * 5 * sizeof(long long), s), "hipMemsetAsync"));
-  const bool vec = W % 8 == 0 && (((uintptr_t)frames | (uintptr_t)ref) & 15) == 0;
+  const bool vec = rows_vectorizable(W, frames, ref);
   const long long per_row = vec ? (x1 + 7) / 8 - x0 / 8 : x1 - x0;
   const long long items = (long long)(y1 - y0) * per_row;
   // workgroups per frame: fill the device when the frames are few, at least 4 items per thread
@@ -313,10 +297,5 @@ extern "C" int kcmc_frame_stats_u16(kcmc_ctx* ctx, const uint16_t* frames, int n
   else
     hipLaunchKernelGGL(frame_stats_kernel<false>, grid, block, 0, s, frames, H, W, ref, y0, y1, x0, x1, o);
   KCMC_TRY(launch_check("frame_stats_u16_kernel"));
-  if (n_frames > 1) {
-    hipLaunchKernelGGL(frame_stats_copy_b_kernel, dim3((unsigned)((n_frames - 1 + kThreads - 1) / kThreads)), block, 0,
-                       s, o, n_frames);
-    return launch_check("frame_stats_copy_b_kernel");
-  }
-  return KCMC_OK;
+  return n_frames > 1 ? launch_copy_b(o, (size_t)n_frames, n_frames, s) : KCMC_OK;
 }

@@ -35,61 +35,14 @@
 // VEC needs frame rows on 16-byte boundaries (W % 8 == 0, 16-byte aligned frames and ref);
 // everything else -- odd widths, a slab view that starts mid-allocation -- gathers the same
 // 8-pixel vectors element by element, every element checked against W.
-#include "kcmc_internal.h"
+#include "u16_rows.h"
 
 namespace kcmc {
 namespace {
 
 constexpr int kThreads = 256;
 
-typedef unsigned long long u64;
 typedef long long i64;
-
-// Lanes of the vector at column c0 (a multiple of 8) outside [x0, x1) read as 0.
-__device__ __forceinline__ uint4 mask8(uint4 q, int c0, int x0, int x1) {
-  if (c0 >= x0 && c0 + 8 <= x1) return q;
-  uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int c = c0 + 2 * k;
-    const uint32_t lo = (c >= x0 && c < x1) ? 0xffffu : 0u;
-    const uint32_t hi = (c + 1 >= x0 && c + 1 < x1) ? 0xffff0000u : 0u;
-    w[k] &= lo | hi;
-  }
-  return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-// The 8 pixels of an image row from column c0 (a multiple of 8, >= 0).  VEC: c0 + 8 <= W.
-template <bool VEC>
-__device__ __forceinline__ uint4 load8(const uint16_t* __restrict__ row, int c0, int W) {
-  if (VEC) return *reinterpret_cast<const uint4*>(row + c0);
-  uint32_t w[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int c = c0 + 2 * k;
-    const uint32_t lo = c < W ? (uint32_t)row[c] : 0u;
-    const uint32_t hi = c + 1 < W ? (uint32_t)row[c + 1] : 0u;
-    w[k] = lo | (hi << 16);
-  }
-  return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-__device__ __forceinline__ void unpack8(const uint4& q, int32_t* v) {
-  v[0] = (int32_t)(q.x & 0xffffu);
-  v[1] = (int32_t)(q.x >> 16);
-  v[2] = (int32_t)(q.y & 0xffffu);
-  v[3] = (int32_t)(q.y >> 16);
-  v[4] = (int32_t)(q.z & 0xffffu);
-  v[5] = (int32_t)(q.z >> 16);
-  v[6] = (int32_t)(q.w & 0xffffu);
-  v[7] = (int32_t)(q.w >> 16);
-}
-
-__device__ __forceinline__ u64 wave_sum(u64 v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-  return v;
-}
 
 // grid (n_sel * n_bands), block 256 = (1 << ct_log2) thread columns x row groups.
 template <bool VEC>
@@ -180,16 +133,9 @@ __global__ __launch_bounds__(kThreads) void gradient_sums_kernel(
     syagx += (u64)(i64)(r0 - cy) * S + ((u64)RB * S - Q);  // sum over the rows of (r0 + i - cy) R_i
   }
 
-  const u64 t[7] = {wave_sum(sa), wave_sum(saa), wave_sum(sab), wave_sum(sagx), wave_sum(sagy), wave_sum(sxagy),
-                    wave_sum(syagx)};
-  if ((tid & 63) == 0)
-    for (int k = 0; k < 7; ++k) red[k][tid >> 6] = t[k];
-  __syncthreads();
-  if (tid < 7) {
-    u64 r = 0;
-    for (int w = 0; w < kThreads / 64; ++w) r += red[tid][w];
-    o[tid] = r;
-  }
+  const u64 v[7] = {sa, saa, sab, sagx, sagy, sxagy, syagx};
+  const u64 r = block_sums(v, red);
+  if (tid < 7) o[tid] = r;
 }
 
 }  // namespace
@@ -204,25 +150,19 @@ using namespace kcmc;
 extern "C" int kcmc_gradient_sums_u16(kcmc_ctx* ctx, const uint16_t* frames, int n_frames, int H, int W,
                                       const int32_t* frame_idx, int n_sel, const uint16_t* ref, int y0, int y1, int x0,
                                       int x1, int band_rows, long long* out, kcmc_stream_t stream) {
-  if (!ctx) return fail(KCMC_EINVAL, "kcmc_gradient_sums_u16: ctx is NULL");
-  if (n_frames < 0 || n_sel < 0 || H <= 0 || W <= 0) return fail(KCMC_EINVAL, "kcmc_gradient_sums_u16: bad shape");
-  if ((long long)H * W >= (1ll << 31)) return fail(KCMC_EINVAL, "kcmc_gradient_sums_u16: H * W must be < 2^31");
-  if (y0 >= y1 || x0 >= x1) return fail(KCMC_EINVAL, "kcmc_gradient_sums_u16: empty rectangle");
-  if (y0 < 1 || x0 < 1 || y1 > H - 1 || x1 > W - 1)
-    return fail(KCMC_EINVAL, "kcmc_gradient_sums_u16: the rectangle grown by 1 leaves the image");
+  KCMC_TRY(check_rect("kcmc_gradient_sums_u16", ctx, n_frames, n_sel, H, W, y0, y1, x0, x1, 1, "1"));
   if (band_rows < 1) return fail(KCMC_EINVAL, "kcmc_gradient_sums_u16: band_rows must be >= 1");
   const unsigned long long w = (unsigned long long)(x1 - x0), h = (unsigned long long)(y1 - y0);
   if ((unsigned long long)band_rows > 0xffffffffull / (w * std::max(w, h)))
     return fail(KCMC_EINVAL, "kcmc_gradient_sums_u16: band_rows * (x1 - x0) * max(x1 - x0, y1 - y0) must be < 2^32");
   if (n_sel == 0) return KCMC_OK;
-  if (!ref || !out || (n_frames > 0 && !frames)) return fail(KCMC_EINVAL, "kcmc_gradient_sums_u16: NULL pointer");
-  if (((uintptr_t)out & 7) != 0) return fail(KCMC_EINVAL, "kcmc_gradient_sums_u16: out must be 8-byte aligned");
+  KCMC_TRY(check_pointers("kcmc_gradient_sums_u16", frames, n_frames, ref, out));
   hipStream_t s = (hipStream_t)stream;
   const long long n_bands = ((long long)h + band_rows - 1) / band_rows;
   const long long blocks = n_bands * n_sel;
   if (blocks > 0x7fffffffll) return fail(KCMC_EUNSUPPORTED, "kcmc_gradient_sums_u16: n_sel * n_bands too large");
 
-  const bool vec = W % 8 == 0 && (((uintptr_t)frames | (uintptr_t)ref) & 15) == 0;
+  const bool vec = rows_vectorizable(W, frames, ref);
   // thread columns: the largest power of two in [8, 256] that idles at most 1/8 of them over
   // the row's vectors, else the one that idles fewest
   const int nvec = (x1 + 7) / 8 - x0 / 8;

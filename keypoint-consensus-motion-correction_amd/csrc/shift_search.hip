@@ -29,7 +29,7 @@
 // element by element into the same LDS image.  No load leaves the image: vectors and
 // elements outside [0, H) x [0, W) are staged as zeros (the contract keeps every pixel a
 // valid shift reads inside the image; the zeros only meet reference zeros).
-#include "kcmc_internal.h"
+#include "u16_rows.h"
 
 namespace kcmc {
 namespace {
@@ -41,33 +41,11 @@ constexpr int kMaxR = 16;
 constexpr int kMaxPasses = 3;      // ceil(33^2 / 512)
 constexpr int kTargetWGs = 1536;   // 256 CUs x 6 resident workgroups of 5 waves
 
-typedef unsigned long long u64;
-
 __device__ __forceinline__ int lds_col0(int R) { return (8 - (R & 7)) & 7; }  // R + lds_col0 is a multiple of 8
-
-// Lanes of the vector at column c0 (a multiple of 8) outside [x0, x1) read as 0.
-__device__ __forceinline__ uint4 mask8(uint4 q, int c0, int x0, int x1) {
-  if (c0 >= x0 && c0 + 8 <= x1) return q;
-  uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int c = c0 + 2 * k;
-    const uint32_t lo = (c >= x0 && c < x1) ? 0xffffu : 0u;
-    const uint32_t hi = (c + 1 >= x0 && c + 1 < x1) ? 0xffff0000u : 0u;
-    w[k] &= lo | hi;
-  }
-  return make_uint4(w[0], w[1], w[2], w[3]);
-}
 
 __device__ __forceinline__ void add_b(u64& sb, u64& sbb, uint32_t b) {
   sb += b;
   sbb += (u64)b * b;
-}
-
-__device__ __forceinline__ u64 wave_sum(u64 v) {
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d, 64);
-  return v;
 }
 
 // grid (n_sel, workgroups per frame), block: a multiple of 64 threads, NP * block >= S^2.
@@ -130,12 +108,7 @@ __global__ __launch_bounds__(kMaxThreads) void shift_search_kernel(
         uint4 q = make_uint4(0u, 0u, 0u, 0u);
         if (gy < y1 && gx < x1 && gx + 8 > x0) {  // inside the image: gx < W, gx and W multiples of 8
           q = mask8(*reinterpret_cast<const uint4*>(ref + (size_t)gy * W + gx), gx, x0, x1);
-          const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            add_b(sb, sbb, w[k] & 0xffffu);
-            add_b(sb, sbb, w[k] >> 16);
-          }
+          for_each_px(q, [&](int, uint32_t b) { add_b(sb, sbb, b); });
         }
         reinterpret_cast<uint4*>(B)[i] = q;
       }
@@ -220,17 +193,6 @@ __global__ __launch_bounds__(kMaxThreads) void shift_search_kernel(
   }
 }
 
-// Sb and Sbb of every frame's shift entry 0 to its other entries (runs after
-// shift_search_kernel on the stream).
-__global__ __launch_bounds__(256) void shift_search_copy_b_kernel(u64* __restrict__ out, size_t n_entries, int S2) {
-  const size_t i = blockIdx.x * (size_t)256 + threadIdx.x;
-  if (i >= n_entries) return;
-  const size_t first = i / S2 * S2;
-  if (i == first) return;
-  out[i * 5 + 1] = out[first * 5 + 1];
-  out[i * 5 + 3] = out[first * 5 + 3];
-}
-
 template <bool VEC>
 void launch(int passes, dim3 grid, dim3 block, size_t lds, hipStream_t s, const uint16_t* frames, int n_frames, int H,
             int W, const int32_t* frame_idx, const uint16_t* ref, int y0, int y1, int x0, int x1, int R, int AW,
@@ -254,23 +216,17 @@ using namespace kcmc;
 extern "C" int kcmc_shift_search_u16(kcmc_ctx* ctx, const uint16_t* frames, int n_frames, int H, int W,
                                      const int32_t* frame_idx, int n_sel, const uint16_t* ref, int y0, int y1, int x0,
                                      int x1, int R, long long* out, kcmc_stream_t stream) {
-  if (!ctx) return fail(KCMC_EINVAL, "kcmc_shift_search_u16: ctx is NULL");
-  if (n_frames < 0 || n_sel < 0 || H <= 0 || W <= 0) return fail(KCMC_EINVAL, "kcmc_shift_search_u16: bad shape");
-  if ((long long)H * W >= (1ll << 31)) return fail(KCMC_EINVAL, "kcmc_shift_search_u16: H * W must be < 2^31");
+  KCMC_TRY(check_rect("kcmc_shift_search_u16", ctx, n_frames, n_sel, H, W, y0, y1, x0, x1, R, "R"));
   if (R < 1 || R > kMaxR) return fail(KCMC_EINVAL, "kcmc_shift_search_u16: R must be in [1, 16]");
-  if (y0 >= y1 || x0 >= x1) return fail(KCMC_EINVAL, "kcmc_shift_search_u16: empty rectangle");
-  if (y0 < R || x0 < R || (long long)y1 + R > H || (long long)x1 + R > W)
-    return fail(KCMC_EINVAL, "kcmc_shift_search_u16: the rectangle grown by R leaves the image");
   if (n_sel == 0) return KCMC_OK;
-  if (!ref || !out || (n_frames > 0 && !frames)) return fail(KCMC_EINVAL, "kcmc_shift_search_u16: NULL pointer");
-  if (((uintptr_t)out & 7) != 0) return fail(KCMC_EINVAL, "kcmc_shift_search_u16: out must be 8-byte aligned");
+  KCMC_TRY(check_pointers("kcmc_shift_search_u16", frames, n_frames, ref, out));
   hipStream_t s = (hipStream_t)stream;
   const int S = 2 * R + 1, S2 = S * S;
   const size_t n_entries = (size_t)n_sel * S2;
   KCMC_TRY(hip_check(hipMemsetAsync(out, 0, n_entries * 5 * sizeof(long long), s), "hipMemsetAsync"));
   if (n_frames == 0) return KCMC_OK;  // every index is out of range
 
-  const bool vec = W % 8 == 0 && (((uintptr_t)frames | (uintptr_t)ref) & 15) == 0;
+  const bool vec = rows_vectorizable(W, frames, ref);
   const int ax0 = (8 - (R & 7)) & 7;
   const int AW = (ax0 + kTW + 2 * R + 7) / 8 * 8, AH = kTH + 2 * R;
   const int tiles_x = (x1 - (x0 & ~7) + kTW - 1) / kTW, tiles_y = (y1 - y0 + kTH - 1) / kTH;
@@ -290,7 +246,5 @@ extern "C" int kcmc_shift_search_u16(kcmc_ctx* ctx, const uint16_t* frames, int 
     launch<false>(passes, grid, block, lds, s, frames, n_frames, H, W, frame_idx, ref, y0, y1, x0, x1, R, AW, tiles_x,
                   (int)tiles, o);
   KCMC_TRY(launch_check("shift_search_kernel"));
-  hipLaunchKernelGGL(shift_search_copy_b_kernel, dim3((unsigned)((n_entries + 255) / 256)), dim3(256), 0, s, o,
-                     n_entries, S2);
-  return launch_check("shift_search_copy_b_kernel");
+  return launch_copy_b(o, n_entries, S2, s);  // Sb, Sbb of every frame's shift entry 0 to its other entries
 }

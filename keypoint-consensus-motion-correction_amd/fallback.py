@@ -27,11 +27,12 @@ from typing import List, NamedTuple, Optional, Sequence
 import numpy as np
 import torch
 
+from . import _intensity as _in
 from . import _lib
 from . import quality as _q
-from .pipeline import _runs, summary_transforms
-from .quality import Frames, Region, _slabs
-from .stages import _ctx, _device_of, _ptr, _stream, warp_affine_u16
+from ._intensity import Frames, Region
+from .pipeline import summary_transforms
+from .stages import warp_affine_u16
 
 MAX_RADIUS = 16
 
@@ -51,32 +52,12 @@ def shift_search(frames: Frames, idx: Sequence[int], ref, region: Region, radius
     frame indices (any order, repeats allowed; an index outside the stack gives a zero row).
     Each slab searches its own frames on its own device.  The region grown by ``radius``
     must stay inside the image."""
-    parts = _slabs(frames)
-    H, W = parts[0].shape[1:]
+    parts = _in._slabs(frames)
     R = check_radius(radius)
     S = 2 * R + 1
-    y0, y1, x0, x1 = (int(v) for v in region)
-    ref_t = ref if isinstance(ref, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(ref))
-    if ref_t.dtype != torch.uint16 or tuple(ref_t.shape) != (H, W):
-        raise ValueError(f"ref must be [{H}, {W}] uint16")
     idx = np.asarray(idx, dtype=np.int64).reshape(-1)
     out = np.zeros((len(idx), S, S, 5), np.int64)
-    L = _lib.load()
-    pending, f0 = [], 0
-    for p in parts:  # queued on every device before any result is read
-        n = p.shape[0]
-        rows = np.flatnonzero((idx >= f0) & (idx < f0 + n))
-        dev = _device_of(p)
-        if len(rows) or not pending:  # the first slab also validates the arguments of an empty search
-            with torch.cuda.device(dev):
-                o = torch.empty((len(rows), S, S, 5), dtype=torch.int64, device=dev)
-                local = torch.from_numpy((idx[rows] - f0).astype(np.int32)).to(dev)
-                r = ref_t.to(dev).contiguous()
-                _lib.check(L.kcmc_shift_search_u16(_ctx(dev).handle, _ptr(p), n, H, W, _ptr(local), len(rows), _ptr(r),
-                                                   y0, y1, x0, x1, R, _ptr(o), _stream(dev)))
-            pending.append((rows, o))
-        f0 += n
-    for rows, o in pending:
+    for rows, o in _in.run_indexed(_lib.load().kcmc_shift_search_u16, parts, idx, ref, region, (R,), (S, S, 5)):
         if len(rows):
             out[rows] = o.cpu().numpy()
     return out
@@ -168,11 +149,7 @@ def correct_skipped(res, sources: Sequence[torch.Tensor], n_images: int, rate: i
     Changes ``res`` in place: the accepted frames' rows of the aligned stack, of ``affines``
     and of the transform summary.  ``res.skipped`` / ``res.interpolated`` stay what they are."""
     R = check_radius(radius)
-    parts = list(res.aligned) if isinstance(res.aligned, (list, tuple)) else [res.aligned]
-    if parts[0].dim() != 3:
-        raise NotImplementedError("the correlation fallback supports grayscale stacks [F, H, W] only")
-    if np.asarray(res.affines).shape[1:] != (2, 3):
-        raise NotImplementedError("the correlation fallback supports 2 x 3 maps only")
+    parts = _in.pass_parts("correlation fallback", res)
     H, W = parts[0].shape[1:]
     skipped = [int(i) for i in res.skipped if 0 <= int(i) < n_images]
     k = len(skipped)
@@ -180,11 +157,8 @@ def correct_skipped(res, sources: Sequence[torch.Tensor], n_images: int, rate: i
     if k == 0:
         return out
     info = logger.info if logger is not None else (lambda msg: None)
-    gone = set(skipped)
-    sel = np.zeros(n_images, bool)
-    sel[[i for i in range(0, n_images, int(rate)) if i not in gone]] = True
     try:
-        ref = _q.mean_image(parts, sel)
+        ref = _q.mean_image(parts, _in.sample_mask(n_images, rate, skipped))
         rect = search_region(_q.valid_region(np.asarray(res.affines)[:n_images], H, W), R)
     except ValueError as e:
         info(f"correlation fallback: nothing corrected ({e})")
@@ -205,18 +179,9 @@ def correct_skipped(res, sources: Sequence[torch.Tensor], n_images: int, rate: i
             new_maps[i] = compose(res.affines[i], pick.dx, pick.dy)
     out.idxs = sorted(new_maps)
     # the accepted frames again, from their source frames, into their rows of the aligned stack
-    f0 = 0
-    for src, dst in zip(sources, parts):
-        n = dst.shape[0]
-        mine = [i for i in out.idxs if f0 <= i < f0 + n]
-        if mine:
-            redo = np.zeros(n, bool)
-            redo[[i - f0 for i in mine]] = True
-            with torch.cuda.device(dst.device):
-                for a, b in _runs(redo):
-                    maps = torch.from_numpy(np.stack([new_maps[f0 + j] for j in range(a, b)])).to(dst.device)
-                    warp_affine_u16(src[a:b], maps, out=dst[a:b])
-        f0 += n
+    for src, dst, f0, a, b in _in.rewarp_runs(sources, parts, out.idxs):
+        maps = torch.from_numpy(np.stack([new_maps[f0 + j] for j in range(a, b)])).to(dst.device)
+        warp_affine_u16(src[a:b], maps, out=dst[a:b])
     for i in out.idxs:
         res.affines[i] = new_maps[i]
         res.euclidean[i] = summary_transforms(new_maps[i][None], model)[0]

@@ -19,27 +19,14 @@ their displacement field is not bounded by its values at the image corners.
 from __future__ import annotations
 
 import math
-from typing import List, Optional, Sequence, Tuple, Union
+from typing import List, Optional, Sequence
 
 import numpy as np
 import torch
 
 from . import _lib
-from .stages import _aligned16, _ctx, _device_of, _ptr, _require, _stream
-
-Frames = Union[torch.Tensor, Sequence[torch.Tensor]]
-Region = Tuple[int, int, int, int]
-
-
-def _slabs(frames: Frames) -> List[torch.Tensor]:
-    parts = [frames] if isinstance(frames, torch.Tensor) else list(frames)
-    if not parts:
-        raise ValueError("no frames")
-    for p in parts:
-        _require(p, "frames", torch.uint16, _device_of(p), 3)
-        if p.shape[1:] != parts[0].shape[1:]:
-            raise ValueError("the slabs of one stack must share H and W")
-    return parts
+from ._intensity import Frames, Region, _slabs, ref_tensor  # noqa: F401  (Frames, Region: this module's API)
+from .stages import _aligned16, _ctx, _device_of, _ptr, _stream
 
 
 def _selection(sel, n_frames: int) -> Optional[np.ndarray]:
@@ -155,9 +142,7 @@ def frame_stats(frames: Frames, ref, region: Region) -> np.ndarray:
     parts = _slabs(frames)
     H, W = parts[0].shape[1:]
     y0, y1, x0, x1 = (int(v) for v in region)
-    ref_t = ref if isinstance(ref, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(ref))
-    if ref_t.dtype != torch.uint16 or tuple(ref_t.shape) != (H, W):
-        raise ValueError(f"ref must be [{H}, {W}] uint16")
+    ref_t = ref_tensor(ref, H, W)
     L = _lib.load()
     outs = []
     for p in parts:

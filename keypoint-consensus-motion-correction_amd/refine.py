@@ -37,12 +37,13 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
+from . import _intensity as _in
 from . import _lib
 from . import fallback as _fb
 from . import quality as _q
+from ._intensity import Frames, Region
 from .pipeline import _runs, summary_transforms
-from .quality import Frames, Region, _slabs
-from .stages import _ctx, _device_of, _ptr, _stream, warp_affine_u16
+from .stages import warp_affine_u16
 
 MOTIONS = ("rigid", "translation")
 _CHUNK = 256  # frames warped and measured at a time (the candidates' scratch)
@@ -88,32 +89,14 @@ def gradient_sums(frames: Frames, idx: Sequence[int], ref, region: Region, rows:
     stack; ``idx``: global frame indices (any order, repeats allowed; an index outside the
     stack gives a zero row).  Each slab sums its own frames on its own device; the kernel's
     bands (``rows`` rows each, default band_rows) are added here, exactly."""
-    parts = _slabs(frames)
+    parts = _in._slabs(frames)
     H, W = parts[0].shape[1:]
-    y0, y1, x0, x1 = _rect(region, H, W)
+    rect = _rect(region, H, W)
     rows = band_rows(H, W, region) if rows is None else int(rows)
-    ref_t = ref if isinstance(ref, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(ref))
-    if ref_t.dtype != torch.uint16 or tuple(ref_t.shape) != (H, W):
-        raise ValueError(f"ref must be [{H}, {W}] uint16")
     idx = np.asarray(idx, dtype=np.int64).reshape(-1)
-    n_bands = -(-(y1 - y0) // max(rows, 1))
+    n_bands = -(-(rect[1] - rect[0]) // max(rows, 1))
     out = np.zeros((len(idx), 7), object)
-    L = _lib.load()
-    pending, f0 = [], 0
-    for p in parts:  # queued on every device before any result is read
-        n = p.shape[0]
-        mine = np.flatnonzero((idx >= f0) & (idx < f0 + n))
-        dev = _device_of(p)
-        if len(mine) or not pending:  # the first slab also validates the arguments of an empty call
-            with torch.cuda.device(dev):
-                o = torch.empty((len(mine), n_bands, 7), dtype=torch.int64, device=dev)
-                local = torch.from_numpy((idx[mine] - f0).astype(np.int32)).to(dev)
-                r = ref_t.to(dev).contiguous()
-                _lib.check(L.kcmc_gradient_sums_u16(_ctx(dev).handle, _ptr(p), n, H, W, _ptr(local), len(mine), _ptr(r),
-                                                    y0, y1, x0, x1, rows, _ptr(o), _stream(dev)))
-            pending.append((mine, o))
-        f0 += n
-    for mine, o in pending:
+    for mine, o in _in.run_indexed(_lib.load().kcmc_gradient_sums_u16, parts, idx, ref, rect, (rows,), (n_bands, 7)):
         if len(mine):
             out[mine] = _add_bands(o.cpu().numpy())
     return out
@@ -290,18 +273,12 @@ def refine_frames(res, sources: Sequence[torch.Tensor], n_images: int, rate: int
     and of the transform summary.  ``res.skipped`` / ``res.interpolated`` stay what they are."""
     check_options(iters, motion, max_step)
     iters = int(iters)
-    parts = list(res.aligned) if isinstance(res.aligned, (list, tuple)) else [res.aligned]
-    if parts[0].dim() != 3:
-        raise NotImplementedError("the intensity refinement supports grayscale stacks [F, H, W] only")
-    if np.asarray(res.affines).shape[1:] != (2, 3):
-        raise NotImplementedError("the intensity refinement supports 2 x 3 maps only")
+    parts = _in.pass_parts("intensity refinement", res)
     H, W = parts[0].shape[1:]
     n = int(n_images)
     out = RefineResult(np.zeros((n, iters, 3)), np.full((n, iters + 1), np.nan), [])
     info = logger.info if logger is not None else (lambda msg: None)
-    gone = set(int(i) for i in res.skipped)
-    sel = np.zeros(n, bool)
-    sel[[i for i in range(0, n, int(rate)) if i not in gone]] = True
+    sel = _in.sample_mask(n, rate, res.skipped)
     changed = set()
     for it in range(iters):
         try:
@@ -320,25 +297,17 @@ def refine_frames(res, sources: Sequence[torch.Tensor], n_images: int, rate: int
         moved = np.flatnonzero((st[:, :3] != 0).any(axis=1))
         new_maps = {int(i): compose_step(res.affines[i], st[i, 0], st[i, 1], st[i, 2], c) for i in moved}
         kept = []
-        f0 = 0
-        for src, dst in zip(sources, parts):  # the candidates, warped from their source frames
-            m = dst.shape[0]
-            mine = np.zeros(m, bool)
-            mine[[i - f0 for i in new_maps if f0 <= i < f0 + m]] = True
-            with torch.cuda.device(dst.device):
-                for a, b in _runs(mine):
-                    for a0 in range(a, b, _CHUNK):
-                        b0 = min(b, a0 + _CHUNK)
-                        maps = torch.from_numpy(np.stack([new_maps[f0 + j] for j in range(a0, b0)])).to(dst.device)
-                        cand = warp_affine_u16(src[a0:b0], maps)
-                        r_new = _q.frame_correlations(cand, ref, rect)
-                        rose = r_new > st[f0 + a0:f0 + b0, 4]  # kept only there (NaN: not kept)
-                        for ra, rb in _runs(rose):
-                            dst[a0 + ra:a0 + rb].copy_(cand[ra:rb])
-                        idx = f0 + a0 + np.flatnonzero(rose)
-                        out.correlations[idx, it + 1] = r_new[rose]
-                        kept.extend(int(i) for i in idx)
-            f0 += m
+        # the candidates, warped from their source frames
+        for src, dst, f0, a, b in _in.rewarp_runs(sources, parts, new_maps, _CHUNK):
+            maps = torch.from_numpy(np.stack([new_maps[f0 + j] for j in range(a, b)])).to(dst.device)
+            cand = warp_affine_u16(src[a:b], maps)
+            r_new = _q.frame_correlations(cand, ref, rect)
+            rose = r_new > st[f0 + a:f0 + b, 4]  # kept only there (NaN: not kept)
+            for ra, rb in _runs(rose):
+                dst[a + ra:a + rb].copy_(cand[ra:rb])
+            idx = f0 + a + np.flatnonzero(rose)
+            out.correlations[idx, it + 1] = r_new[rose]
+            kept.extend(int(i) for i in idx)
         if kept:
             maps = np.stack([new_maps[i] for i in kept])
             res.affines[kept] = maps

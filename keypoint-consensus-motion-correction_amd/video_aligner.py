@@ -30,6 +30,7 @@ import numpy as np
 import torch
 
 from . import affines as _aff
+from . import _intensity as _in
 from . import fallback as _fb
 from . import multidevice as _md
 from . import piecewise as _pw
@@ -292,6 +293,15 @@ class VideoAligner:
         if self.patch_residuals is not None:  # the maps the field was added to
             self.affines = res.affines
 
+    def _check_intensity_pass(self, switch: str, why: str, images) -> None:
+        """What the fallback and the refinement both refuse (``why``: what rules a homography out)."""
+        if self.RANSAC_MODEL == "projective":
+            raise NotImplementedError(f"{switch} does not support RANSAC_MODEL = 'projective' ({why})")
+        if self.PIECEWISE_GRID is not None:
+            raise NotImplementedError(f"{switch} does not run together with PIECEWISE_GRID")
+        if getattr(images, "ndim", 3) != 3:
+            raise NotImplementedError(f"{switch} supports grayscale stacks [F, H, W] only")
+
     # ------------------------------------------- intensity fallback for frames without a model
     def _reset_fallback(self) -> None:
         self.fallback_shifts = None
@@ -306,13 +316,7 @@ class VideoAligner:
         if self.FALLBACK != "correlation":
             raise ValueError(f"FALLBACK must be 'interpolate' or 'correlation', got {self.FALLBACK!r}")
         _fb.check_radius(self.FALLBACK_RADIUS)
-        if self.RANSAC_MODEL == "projective":
-            raise NotImplementedError("FALLBACK = 'correlation' does not support RANSAC_MODEL = 'projective' (the "
-                                      "shift is composed with a 2 x 3 map)")
-        if self.PIECEWISE_GRID is not None:
-            raise NotImplementedError("FALLBACK = 'correlation' does not run together with PIECEWISE_GRID")
-        if getattr(images, "ndim", 3) != 3:
-            raise NotImplementedError("FALLBACK = 'correlation' supports grayscale stacks [F, H, W] only")
+        self._check_intensity_pass("FALLBACK = 'correlation'", "the shift is composed with a 2 x 3 map", images)
         return True
 
     def _with_fallback(self, hot: Callable, slabs: Sequence[_pl.SlabInputs], n_images: int, rate: int) -> Callable:
@@ -350,13 +354,7 @@ class VideoAligner:
             _rf.check_options(self.REFINE_ITERS, self.REFINE_MOTION, self.REFINE_MAX_STEP)
         except ValueError as e:
             raise ValueError(f"REFINE_ITERS / REFINE_MOTION / REFINE_MAX_STEP: {e}") from None
-        if self.RANSAC_MODEL == "projective":
-            raise NotImplementedError("REFINE = 'intensity' does not support RANSAC_MODEL = 'projective' (the "
-                                      "step is composed with a 2 x 3 map)")
-        if self.PIECEWISE_GRID is not None:
-            raise NotImplementedError("REFINE = 'intensity' does not run together with PIECEWISE_GRID")
-        if getattr(images, "ndim", 3) != 3:
-            raise NotImplementedError("REFINE = 'intensity' supports grayscale stacks [F, H, W] only")
+        self._check_intensity_pass("REFINE = 'intensity'", "the step is composed with a 2 x 3 map", images)
         return True
 
     def _with_refine(self, hot: Callable, slabs: Sequence[_pl.SlabInputs], n_images: int, rate: int) -> Callable:
@@ -401,14 +399,11 @@ class VideoAligner:
     def _measure(self, res, n_images: int, rate: int) -> List[int]:
         """The metrics of one pass (res: a SlabResult or SplitResult, frames still on their
         devices and unpatched); returns sel0, the sample frames that got a model of their own."""
-        parts = res.aligned if isinstance(res.aligned, (list, tuple)) else [res.aligned]
+        parts = _in.parts_of(res)
         if parts[0].dim() != 3:
             raise NotImplementedError("QUALITY_METRICS / TEMPLATE_REFINE_ITERS support grayscale stacks [F, H, W] only")
         H, W = parts[0].shape[1:]
-        skipped = set(int(i) for i in res.skipped)
-        sel0 = [i for i in range(0, n_images, rate) if i not in skipped]
-        sel = np.zeros(n_images, bool)
-        sel[sel0] = True
+        sel = _in.sample_mask(n_images, rate, res.skipped)
         mean0 = _q.mean_image(parts, sel)
         self.affines = res.affines
         region = _q.valid_region(np.asarray(res.affines)[:n_images], H, W)
@@ -423,7 +418,7 @@ class VideoAligner:
             self.logger.info(f"pass {len(self.correlation_history)}: mean frame correlation with the mean image "
                              f"{np.nanmean(corr):.6f} over rows [{region[0]}, {region[1]}), columns "
                              f"[{region[2]}, {region[3]})")
-        return sel0
+        return np.flatnonzero(sel).tolist()
 
     def _run_passes(self, hot: Callable, slabs: Sequence[_pl.SlabInputs], n_images: int, rate: int,
                     detect_template: Optional[Callable] = None):
@@ -445,10 +440,9 @@ class VideoAligner:
                 raise
             if k == iters:
                 break
-            parts = res.aligned if isinstance(res.aligned, (list, tuple)) else [res.aligned]
             best = np.zeros(n_images, bool)
             best[_q.select_top(self.frame_correlations, sel0, float(self.TEMPLATE_REFINE_TOP_FRAC))] = True
-            self.template_image = _q.mean_image(parts, best).cpu().numpy()
+            self.template_image = _q.mean_image(_in.parts_of(res), best).cpu().numpy()
             kp, des = detect_template(self.template_image)
             self._kp_template = np.asarray(kp, np.float64).reshape(-1, 2)
             self._des_template = np.asarray(des, np.uint8)
