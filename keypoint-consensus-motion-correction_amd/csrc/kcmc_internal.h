@@ -81,8 +81,8 @@ int workspace_alloc(kcmc_ctx* ctx, void** p, size_t bytes, hipStream_t s);
 // bytes > 0: the block may be kept as the stream's cached workspace (see kcmc_ctx).
 int workspace_free(kcmc_ctx* ctx, void* p, hipStream_t s, size_t bytes = 0);
 
-// VA:196-214 per frame on knn output (match.hip): reorder, ratio and displacement
-// filters, survivor bitmask, log counts.  Shared by the uint8 and float32 matchers.
+// VA:196-214 per frame on knn output (match_filter.hip): reorder, ratio and displacement
+// filters, survivor bitmask, log counts.  Shared by the three matchers.
 int launch_match_filter(const int32_t* idx, const float* dist, const double* kp_tpl, const double* kp_q,
                         const int32_t* q_off, int n_frames, int n_tpl, double ratio, double d_lo, double d_hi,
                         double* kp_ordered, uint32_t* keep_bits, int32_t* counts, hipStream_t s);

@@ -1,7 +1,8 @@
-// K1: batched k=2 L2 matching of uint8 descriptors + the per-frame match filters.
+// K1: batched k=2 L2 matching of uint8 descriptors (the per-frame match filters that
+// follow it are in match_filter.hip).
 //
-// Reference: VA:194-214 (cv2.BFMatcher(crossCheck=False).knnMatch(des_template,
-// des_query, k=2), best-match reorder, ratio filter, median displacement filter).
+// Reference: VA:194-195 (cv2.BFMatcher(crossCheck=False).knnMatch(des_template,
+// des_query, k=2)).
 //
 // knn2_l2u8_kernel -- persistent: a workgroup keeps 256 / 512 template rows in registers
 //   and matches them against a strided set of frames.
@@ -27,16 +28,12 @@
 //   (ssd << 32 | j) top-2 with SSD = (key >> 8) + T - B.  Frame descriptors are staged
 //   through LDS (converted to int8, zero-padded to DP, rows padded by 16 B so the
 //   ds_read_b128 fragment reads are bank-conflict free).
-//
-// match_filter_kernel -- one workgroup per frame: VA:196-214 in float64 with the
-//   reference's exact operation order (no FMA contraction; file built with
-//   -ffp-contract=off), median by an LDS bitonic sort.
 #include <cfloat>
 #include <climits>
 
 #include <atomic>
 
-#include "kcmc_internal.h"
+#include "match_common.h"
 
 namespace kcmc {
 
@@ -75,12 +72,6 @@ constexpr int kBias = 1 << 20;
 static_assert(64 * 128 * 128 <= kBias, "kBias must cover the largest template term T");
 static_assert(((64ull * 255 * 255) << 8 | 0xffull) < kPad, "real keys (SSD << 8 | row) must stay below kPad");
 constexpr unsigned long long kNoKey64 = ~0ull;
-
-__device__ __forceinline__ uint32_t med3_u32(uint32_t a, uint32_t b, uint32_t c) {
-  uint32_t r;
-  asm("v_med3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-}
 
 __device__ __forceinline__ uint32_t min3_u32(uint32_t a, uint32_t b, uint32_t c) {
   uint32_t r;
@@ -140,12 +131,6 @@ struct RowPieces {
   static constexpr int kNP = DP / 16;
 };
 
-__device__ __forceinline__ uint4 load16(const uint8_t* p) {
-  uint4 v;
-  __builtin_memcpy(&v, p, 16);  // global_load_dwordx4 (unaligned access is allowed for global memory)
-  return v;
-}
-
 template <int DP>
 __device__ __forceinline__ void issue_row(const uint8_t* __restrict__ row, int D, bool last_row,
                                           uint4 (&pf)[RowPieces<DP>::kNP]) {
@@ -162,12 +147,6 @@ __device__ __forceinline__ void issue_row(const uint8_t* __restrict__ row, int D
     for (int k = 0; k < NP; ++k)  // (a register array is never indexed at run time)
       if (k == np - 1) pf[k] = make_uint4(w[0], w[1], w[2], w[3]);
   }
-}
-
-// mask of the bytes of word `w` (0..3) of piece `k` that lie inside the descriptor
-__device__ __forceinline__ uint32_t byte_mask(int D, int k, int w) {
-  const int n = D - 16 * k - 4 * w;  // bytes of this word inside the row
-  return n >= 4 ? ~0u : (n <= 0 ? 0u : (1u << (8 * n)) - 1u);
 }
 
 template <int DP>
@@ -357,349 +336,6 @@ __global__ __launch_bounds__(KnnShape<WAVES>::kThreads) void knn2_l2u8_kernel(
   }
 }
 
-// ------------------------------------------------------------ per-frame filters
-constexpr int kFilterThreads = 256;
-
-__global__ __launch_bounds__(kFilterThreads) void match_filter_kernel(
-    const int32_t* __restrict__ idx, const float* __restrict__ dist, const double* __restrict__ kp_tpl,
-    const double* __restrict__ kp_q, const int32_t* __restrict__ q_off, int n_tpl, double ratio,
-    double d_lo, double d_hi, double* __restrict__ kp_ordered, uint32_t* __restrict__ keep_bits,
-    int32_t* __restrict__ counts) {
-  extern __shared__ __attribute__((aligned(16))) double sdisp[];  // [pow2 >= n_tpl]
-  __shared__ int s_nratio;
-  __shared__ int s_ndist;
-  const int f = blockIdx.x;
-  const int tid = threadIdx.x;
-  const int q_begin = q_off[f];
-  const int words = (n_tpl + 31) >> 5;
-  if (tid == 0) {
-    s_nratio = 0;
-    s_ndist = 0;
-  }
-  __syncthreads();
-
-  // pass 1: reorder (VA:197-200), ratio filter (VA:202-203), displacement of survivors (VA:208)
-  for (int i = tid; i < n_tpl; i += kFilterThreads) {
-    const size_t o = ((size_t)f * n_tpl + i) * 2;
-    const int j0 = idx[o];
-    double qx = 0.0, qy = 0.0;
-    if (j0 >= 0) {
-      qx = kp_q[2 * (size_t)(q_begin + j0)];
-      qy = kp_q[2 * (size_t)(q_begin + j0) + 1];
-    }
-    kp_ordered[((size_t)f * n_tpl + i) * 2] = qx;
-    kp_ordered[((size_t)f * n_tpl + i) * 2 + 1] = qy;
-    const bool ok = (double)dist[o] < ratio * (double)dist[o + 1];
-    if (ok) {
-      const double dx = kp_tpl[2 * i] - qx, dy = kp_tpl[2 * i + 1] - qy;
-      const int p = atomicAdd(&s_nratio, 1);
-      sdisp[p] = sqrt(dx * dx + dy * dy);
-    }
-  }
-  __syncthreads();
-  const int nr = s_nratio;
-  int P = 1;
-  while (P < nr) P <<= 1;
-  for (int i = nr + tid; i < P; i += kFilterThreads) sdisp[i] = INFINITY;
-  __syncthreads();
-  // bitonic sort of the nr ratio-survivor displacements (np.median, VA:210)
-  for (int k = 2; k <= P; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < P; i += kFilterThreads) {
-        const int ixj = i ^ j;
-        if (ixj > i) {
-          const double a = sdisp[i], b = sdisp[ixj];
-          const bool up = (i & k) == 0;
-          if ((a > b) == up) {
-            sdisp[i] = b;
-            sdisp[ixj] = a;
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
-  double med = 0.0;
-  if (nr > 0) med = (nr & 1) ? sdisp[nr >> 1] : (sdisp[(nr >> 1) - 1] + sdisp[nr >> 1]) / 2.0;
-  const double lo = d_lo * med, hi = d_hi * med;
-
-  // pass 2: keep = ratio survivor and lo <= d <= hi (VA:210); bitmask + counts
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  for (int base = 0; base < n_tpl; base += kFilterThreads) {
-    const int i = base + tid;
-    bool keep = false;
-    if (i < n_tpl && nr > 0) {
-      const size_t o = ((size_t)f * n_tpl + i) * 2;
-      const bool ok = (double)dist[o] < ratio * (double)dist[o + 1];
-      if (ok) {
-        const double qx = kp_ordered[((size_t)f * n_tpl + i) * 2];
-        const double qy = kp_ordered[((size_t)f * n_tpl + i) * 2 + 1];
-        const double dx = kp_tpl[2 * i] - qx, dy = kp_tpl[2 * i + 1] - qy;
-        const double d = sqrt(dx * dx + dy * dy);
-        keep = (lo <= d) && (d <= hi);
-      }
-    }
-    const unsigned long long m = __ballot(keep);
-    const int w0 = (base + wave * 64) >> 5;
-    if (lane == 0) {
-      if (w0 < words) keep_bits[(size_t)f * words + w0] = (uint32_t)m;
-      if (w0 + 1 < words) keep_bits[(size_t)f * words + w0 + 1] = (uint32_t)(m >> 32);
-      if (m) atomicAdd(&s_ndist, __popcll(m));
-    }
-  }
-  __syncthreads();
-  if (tid == 0) {
-    counts[4 * (size_t)f + 0] = n_tpl;  // len(kp_query) after the reorder at VA:200
-    counts[4 * (size_t)f + 1] = n_tpl;  // len(matches)
-    counts[4 * (size_t)f + 2] = nr;
-    counts[4 * (size_t)f + 3] = s_ndist;
-  }
-}
-
-// The same filters for n_tpl <= 512 with ONE wave per frame and no barrier: template i =
-// 64 k + lane sits in the lane's register k (k < 8), and the median of the ratio survivors
-// comes from a bitonic sort of all 512 register slots (non-survivors +inf) across the wave
-// (stride < 8: within a lane; >= 8: shuffles with lane ^ stride / 8), so the survivors need
-// no compaction: the sorted slots 0 .. nr - 1 are their sorted displacements.  The
-// barrier-per-stage sort of the workgroup kernel waited ~40 us per launch at c2 / c3.
-constexpr int kFilterWaveFrames = 4;  // frames (waves) per 256-thread workgroup
-
-__device__ __forceinline__ void cmpx(double& a, double& b, bool asc) {
-  const double lo = fmin(a, b), hi = fmax(a, b);
-  a = asc ? lo : hi;
-  b = asc ? hi : lo;
-}
-
-__global__ __launch_bounds__(64 * kFilterWaveFrames) void match_filter_wave_kernel(
-    const int32_t* __restrict__ idx, const float* __restrict__ dist, const double* __restrict__ kp_tpl,
-    const double* __restrict__ kp_q, const int32_t* __restrict__ q_off, int n_frames, int n_tpl, double ratio,
-    double d_lo, double d_hi, double* __restrict__ kp_ordered, uint32_t* __restrict__ keep_bits,
-    int32_t* __restrict__ counts) {
-  const int lane = threadIdx.x & 63;
-  const int f = blockIdx.x * kFilterWaveFrames + (threadIdx.x >> 6);
-  if (f >= n_frames) return;  // the whole wave
-  const int q_begin = q_off[f];
-  const int words = (n_tpl + 31) >> 5;
-  // pass 1: reorder (VA:197-200), ratio filter (VA:202-203), displacement of survivors (VA:208)
-  double dv[8];
-  uint64_t okm[8];
-  int nr = 0;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const int i = 64 * k + lane;
-    bool ok = false;
-    double d = INFINITY;
-    if (i < n_tpl) {
-      const size_t o = ((size_t)f * n_tpl + i) * 2;
-      const int j0 = idx[o];
-      double qx = 0.0, qy = 0.0;
-      if (j0 >= 0) {
-        qx = kp_q[2 * (size_t)(q_begin + j0)];
-        qy = kp_q[2 * (size_t)(q_begin + j0) + 1];
-      }
-      kp_ordered[((size_t)f * n_tpl + i) * 2] = qx;
-      kp_ordered[((size_t)f * n_tpl + i) * 2 + 1] = qy;
-      ok = (double)dist[o] < ratio * (double)dist[o + 1];
-      if (ok) {
-        const double dx = kp_tpl[2 * i] - qx, dy = kp_tpl[2 * i + 1] - qy;
-        d = sqrt(dx * dx + dy * dy);
-      }
-    }
-    dv[k] = d;
-    okm[k] = __ballot(ok);
-    nr += __popcll(okm[k]);
-  }
-  // bitonic sort (ascending) of the 512 slots e = 8 lane + k
-  double v[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) v[k] = dv[k];
-#pragma unroll
-  for (int size = 2; size <= 512; size <<= 1) {
-#pragma unroll
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      if (stride >= 8) {
-        const int ls = stride >> 3;
-        const bool lower = (lane & ls) == 0;
-        const bool asc = size >= 16 ? (lane & (size >> 3)) == 0 : true;  // (e & size) == 0
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const double o = __shfl_xor(v[k], ls, 64);
-          v[k] = (lower == asc) ? fmin(v[k], o) : fmax(v[k], o);
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          if ((k & stride) == 0) {
-            const bool asc = size >= 8 ? (lane & (size >> 3)) == 0 : (k & size) == 0;  // (e & size) == 0
-            cmpx(v[k], v[k | stride], asc);
-          }
-        }
-      }
-    }
-  }
-  // the median of the nr survivors: sorted slots (nr - 1) / 2 and nr / 2 (np.median, VA:210)
-  double med = 0.0;
-  if (nr > 0) {
-    auto slot = [&](int e) -> double {
-      double x = v[0];
-#pragma unroll
-      for (int k = 1; k < 8; ++k)
-        if ((e & 7) == k) x = v[k];  // wave-uniform
-      return __shfl(x, e >> 3, 64);
-    };
-    const double b = slot(nr >> 1);
-    med = (nr & 1) ? b : (slot((nr >> 1) - 1) + b) / 2.0;
-  }
-  const double lo = d_lo * med, hi = d_hi * med;
-  // pass 2: keep = ratio survivor and lo <= d <= hi (VA:210); bitmask + counts
-  int nk = 0;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const bool keep = nr > 0 && ((okm[k] >> lane) & 1ull) && lo <= dv[k] && dv[k] <= hi;
-    const uint64_t m = __ballot(keep);
-    nk += __popcll(m);
-    if (lane == 0) {
-      if (2 * k < words) keep_bits[(size_t)f * words + 2 * k] = (uint32_t)m;
-      if (2 * k + 1 < words) keep_bits[(size_t)f * words + 2 * k + 1] = (uint32_t)(m >> 32);
-    }
-  }
-  if (lane == 0) {
-    counts[4 * (size_t)f + 0] = n_tpl;  // len(kp_query) after the reorder at VA:200
-    counts[4 * (size_t)f + 1] = n_tpl;  // len(matches)
-    counts[4 * (size_t)f + 2] = nr;
-    counts[4 * (size_t)f + 3] = nk;
-  }
-}
-
-// The same for 512 < n_tpl <= 4096: one 512-thread workgroup per frame, template
-// i = 512 k + tid in register k of thread tid, and a 4096-slot bitonic sort (slot
-// e = 8 tid + k): strides < 8 within a thread, < 512 by shuffles inside a wave, and only
-// the strides 512..2048 (6 of the 78 stages) through LDS with barriers (the workgroup
-// kernel above synchronises at all 78).
-constexpr int kFilterWgThreads = 512;
-
-__global__ __launch_bounds__(kFilterWgThreads) void match_filter_wg_kernel(
-    const int32_t* __restrict__ idx, const float* __restrict__ dist, const double* __restrict__ kp_tpl,
-    const double* __restrict__ kp_q, const int32_t* __restrict__ q_off, int n_tpl, double ratio, double d_lo,
-    double d_hi, double* __restrict__ kp_ordered, uint32_t* __restrict__ keep_bits, int32_t* __restrict__ counts) {
-  __shared__ double sx[kFilterWgThreads * 8];
-  __shared__ int s_cnt[kFilterWgThreads / 64];
-  __shared__ double s_med[2];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int f = blockIdx.x;
-  const int q_begin = q_off[f];
-  const int words = (n_tpl + 31) >> 5;
-  double dv[8];
-  uint64_t okm[8];
-  int nr = 0;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const int i = kFilterWgThreads * k + tid;
-    bool ok = false;
-    double d = INFINITY;
-    if (i < n_tpl) {
-      const size_t o = ((size_t)f * n_tpl + i) * 2;
-      const int j0 = idx[o];
-      double qx = 0.0, qy = 0.0;
-      if (j0 >= 0) {
-        qx = kp_q[2 * (size_t)(q_begin + j0)];
-        qy = kp_q[2 * (size_t)(q_begin + j0) + 1];
-      }
-      kp_ordered[((size_t)f * n_tpl + i) * 2] = qx;
-      kp_ordered[((size_t)f * n_tpl + i) * 2 + 1] = qy;
-      ok = (double)dist[o] < ratio * (double)dist[o + 1];
-      if (ok) {
-        const double dx = kp_tpl[2 * i] - qx, dy = kp_tpl[2 * i + 1] - qy;
-        d = sqrt(dx * dx + dy * dy);
-      }
-    }
-    dv[k] = d;
-    okm[k] = __ballot(ok);
-    nr += __popcll(okm[k]);
-  }
-  if (lane == 0) s_cnt[wave] = nr;
-  __syncthreads();
-  nr = 0;
-#pragma unroll
-  for (int w = 0; w < kFilterWgThreads / 64; ++w) nr += s_cnt[w];
-  double v[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) v[k] = dv[k];
-#pragma unroll
-  for (int size = 2; size <= 8 * kFilterWgThreads; size <<= 1) {
-    const bool asc_t = (tid & (size >> 3)) == 0;  // (e & size) == 0 for size >= 8
-#pragma unroll
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      if (stride >= 512) {  // partner in another wave: through LDS
-        const int ts = stride >> 3;
-        const bool lower = (tid & ts) == 0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) sx[8 * tid + k] = v[k];
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const double o = sx[8 * (tid ^ ts) + k];
-          v[k] = (lower == asc_t) ? fmin(v[k], o) : fmax(v[k], o);
-        }
-        __syncthreads();
-      } else if (stride >= 8) {
-        const int ls = stride >> 3;
-        const bool lower = (tid & ls) == 0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const double o = __shfl_xor(v[k], ls, 64);
-          v[k] = (lower == asc_t) ? fmin(v[k], o) : fmax(v[k], o);
-        }
-      } else {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          if ((k & stride) == 0) {
-            const bool asc = size >= 8 ? asc_t : (k & size) == 0;
-            cmpx(v[k], v[k | stride], asc);
-          }
-        }
-      }
-    }
-  }
-  // the median of the nr survivors: sorted slots (nr - 1) / 2 and nr / 2 (np.median, VA:210)
-  if (nr > 0) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int e = 8 * tid + k;
-      if (e == (nr >> 1)) s_med[1] = v[k];
-      if ((nr & 1) == 0 && e == (nr >> 1) - 1) s_med[0] = v[k];
-    }
-  }
-  __syncthreads();
-  double med = 0.0;
-  if (nr > 0) med = (nr & 1) ? s_med[1] : (s_med[0] + s_med[1]) / 2.0;
-  const double lo = d_lo * med, hi = d_hi * med;
-  int nk = 0;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const bool keep = nr > 0 && ((okm[k] >> lane) & 1ull) && lo <= dv[k] && dv[k] <= hi;
-    const uint64_t m = __ballot(keep);
-    nk += __popcll(m);
-    const int w0 = (kFilterWgThreads * k + 64 * wave) >> 5;
-    if (lane == 0) {
-      if (w0 < words) keep_bits[(size_t)f * words + w0] = (uint32_t)m;
-      if (w0 + 1 < words) keep_bits[(size_t)f * words + w0 + 1] = (uint32_t)(m >> 32);
-    }
-  }
-  __syncthreads();  // s_cnt is reused
-  if (lane == 0) s_cnt[wave] = nk;
-  __syncthreads();
-  if (tid == 0) {
-    int tot = 0;
-    for (int w = 0; w < kFilterWgThreads / 64; ++w) tot += s_cnt[w];
-    counts[4 * (size_t)f + 0] = n_tpl;
-    counts[4 * (size_t)f + 1] = n_tpl;
-    counts[4 * (size_t)f + 2] = nr;
-    counts[4 * (size_t)f + 3] = tot;
-  }
-}
-
 // persistent grid: n_tg template groups x G frame strides, G = the resident workgroups
 // per template group (workgroups never wait on each other, so a wrong residency count
 // costs balance, not progress)
@@ -740,39 +376,12 @@ int launch_knn(const uint8_t* des_tpl, int n_tpl, int D, const uint8_t* des_q, c
 
 int check_match_args(const void* des_tpl, int n_tpl, int D, const void* des_q, const void* q_off,
                      int n_frames, int max_nq, const void* o1, const void* o2) {
-  if (n_tpl < 0 || n_frames < 0 || max_nq < 0) return fail(KCMC_EINVAL, "match: negative size");
-  if (D < 1 || D > 64)
-    return fail(KCMC_EUNSUPPORTED, "match: descriptor length D must be in [1, 64] (got " + std::to_string(D) + ")");
-  if (max_nq > (1 << 30)) return fail(KCMC_EUNSUPPORTED, "match: max_nq too large");
-  if (n_frames > 65535) return fail(KCMC_EUNSUPPORTED, "match: at most 65535 frames per call");
-  if (n_frames > 0 && n_tpl > 0 && (!des_tpl || !q_off || !o1 || !o2 || (max_nq > 0 && !des_q)))
-    return fail(KCMC_EINVAL, "match: NULL pointer");
-  return KCMC_OK;
+  return check_knn_args("match", 64, des_tpl, n_tpl, D, des_q, q_off, n_frames, max_nq, o1, o2, [&] {
+    return max_nq > (1 << 30) ? fail(KCMC_EUNSUPPORTED, "match: max_nq too large") : KCMC_OK;
+  });
 }
 
 }  // namespace
-
-int launch_match_filter(const int32_t* idx, const float* dist, const double* kp_tpl, const double* kp_q,
-                        const int32_t* q_off, int n_frames, int n_tpl, double ratio, double d_lo, double d_hi,
-                        double* kp_ordered, uint32_t* keep_bits, int32_t* counts, hipStream_t s) {
-  if (n_tpl <= 512) {
-    hipLaunchKernelGGL(match_filter_wave_kernel, dim3(ceil_div(n_frames, kFilterWaveFrames)),
-                       dim3(64 * kFilterWaveFrames), 0, s, idx, dist, kp_tpl, kp_q, q_off, n_frames, n_tpl, ratio,
-                       d_lo, d_hi, kp_ordered, keep_bits, counts);
-    return launch_check("match_filter_wave_kernel");
-  }
-  if (n_tpl <= 8 * kFilterWgThreads) {
-    hipLaunchKernelGGL(match_filter_wg_kernel, dim3(n_frames), dim3(kFilterWgThreads), 0, s, idx, dist, kp_tpl, kp_q,
-                       q_off, n_tpl, ratio, d_lo, d_hi, kp_ordered, keep_bits, counts);
-    return launch_check("match_filter_wg_kernel");
-  }
-  int P = 1;
-  while (P < n_tpl) P <<= 1;
-  hipLaunchKernelGGL(match_filter_kernel, dim3(n_frames), dim3(kFilterThreads), (size_t)P * sizeof(double), s, idx,
-                     dist, kp_tpl, kp_q, q_off, n_tpl, ratio, d_lo, d_hi, kp_ordered, keep_bits, counts);
-  return launch_check("match_filter_kernel");
-}
-
 }  // namespace kcmc
 
 using namespace kcmc;
@@ -792,27 +401,10 @@ extern "C" int kcmc_match_frames(kcmc_ctx* ctx, const uint8_t* des_tpl, const do
                                  int32_t* out_counts, kcmc_stream_t stream) {
   if (!ctx) return fail(KCMC_EINVAL, "kcmc_match_frames: ctx is NULL");
   KCMC_TRY(check_match_args(des_tpl, n_tpl, D, des_q, q_off, n_frames, max_nq, out_idx, out_dist));
-  if (n_frames > 0 && n_tpl > 0 && (!kp_tpl || !out_kp_ordered || !out_keep_bits || !out_counts || (max_nq > 0 && !kp_q)))
-    return fail(KCMC_EINVAL, "kcmc_match_frames: NULL pointer");
-  if (n_tpl > 8192) return fail(KCMC_EUNSUPPORTED, "kcmc_match_frames: n_tpl > 8192");
-  if (n_frames == 0 || n_tpl == 0) return KCMC_OK;
   hipStream_t s = (hipStream_t)stream;
-  KCMC_TRY(launch_knn(des_tpl, n_tpl, D, des_q, q_off, n_frames, max_nq, out_idx, out_dist, s));
-  return launch_match_filter(out_idx, out_dist, kp_tpl, kp_q, q_off, n_frames, n_tpl, ratio, d_lo, d_hi,
-                             out_kp_ordered, out_keep_bits, out_counts, s);
-}
-
-extern "C" int kcmc_match_filter(kcmc_ctx* ctx, const int32_t* idx, const float* dist, const double* kp_tpl,
-                                 const double* kp_q, const int32_t* q_off, int n_frames, int n_tpl, double ratio,
-                                 double d_lo, double d_hi, double* out_kp_ordered, uint32_t* out_keep_bits,
-                                 int32_t* out_counts, kcmc_stream_t stream) {
-  if (!ctx) return fail(KCMC_EINVAL, "kcmc_match_filter: ctx is NULL");
-  if (n_tpl < 0 || n_frames < 0) return fail(KCMC_EINVAL, "kcmc_match_filter: negative size");
-  if (n_frames > 65535) return fail(KCMC_EUNSUPPORTED, "kcmc_match_filter: at most 65535 frames per call");
-  if (n_tpl > 8192) return fail(KCMC_EUNSUPPORTED, "kcmc_match_filter: n_tpl > 8192");
-  if (n_frames == 0 || n_tpl == 0) return KCMC_OK;
-  if (!idx || !dist || !kp_tpl || !kp_q || !q_off || !out_kp_ordered || !out_keep_bits || !out_counts)
-    return fail(KCMC_EINVAL, "kcmc_match_filter: NULL pointer");
-  return launch_match_filter(idx, dist, kp_tpl, kp_q, q_off, n_frames, n_tpl, ratio, d_lo, d_hi, out_kp_ordered,
-                             out_keep_bits, out_counts, (hipStream_t)stream);
+  return match_frames_tail(
+      "kcmc_match_frames",
+      [&] { return launch_knn(des_tpl, n_tpl, D, des_q, q_off, n_frames, max_nq, out_idx, out_dist, s); }, kp_tpl,
+      kp_q, q_off, n_frames, n_tpl, max_nq, ratio, d_lo, d_hi, out_idx, out_dist, out_kp_ordered, out_keep_bits,
+      out_counts, s);
 }

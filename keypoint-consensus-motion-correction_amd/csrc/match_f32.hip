@@ -38,7 +38,7 @@
 //   list, which knn2_l2f32_fallback_kernel finishes by exact brute force.
 #include <cfloat>
 
-#include "kcmc_internal.h"
+#include "match_common.h"
 
 namespace kcmc {
 namespace {
@@ -111,19 +111,6 @@ __device__ __forceinline__ void top2_insert_exact(float& d0, int& j0, float& d1,
     d1 = d;
     j1 = j;
   }
-}
-
-// Workgroups are dealt round-robin over the 8 XCDs: give each XCD a contiguous run of
-// ids (bijective also when n % 8 != 0).
-__device__ __forceinline__ int xcd_remap(int bid, int n) {
-  const int q8 = n >> 3, r8 = n & 7, xcd = bid & 7;
-  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-}
-
-__device__ __forceinline__ uint32_t med3_u32(uint32_t a, uint32_t b, uint32_t c) {
-  uint32_t r;
-  asm("v_med3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
 }
 
 // Sorted top-kTop of 32-bit keys (k0 <= k1 <= ...): kTop VALU per insertion.
@@ -826,14 +813,12 @@ __global__ __launch_bounds__(256) void knn2_l2f32_fallback_out_kernel(int n_tpl,
 
 int check_f32_args(const void* des_tpl, int n_tpl, int D, const void* des_q, const void* q_off, int n_frames,
                    int max_nq, const void* o1, const void* o2) {
-  if (n_tpl < 0 || n_frames < 0 || max_nq < 0) return fail(KCMC_EINVAL, "match_f32: negative size");
-  if (D < 1 || D > kDP)
-    return fail(KCMC_EUNSUPPORTED, "match_f32: descriptor length D must be in [1, 128] (got " + std::to_string(D) + ")");
-  if (n_frames > 65535) return fail(KCMC_EUNSUPPORTED, "match_f32: at most 65535 frames per call");
-  if ((long long)n_frames * n_tpl >= (1ll << 31)) return fail(KCMC_EUNSUPPORTED, "match_f32: n_frames * n_tpl too large");
-  if (n_frames > 0 && n_tpl > 0 && (!des_tpl || !q_off || !o1 || !o2 || (max_nq > 0 && !des_q)))
-    return fail(KCMC_EINVAL, "match_f32: NULL pointer");
-  return KCMC_OK;
+  return check_knn_args("match_f32", kDP, des_tpl, n_tpl, D, des_q, q_off, n_frames, max_nq, o1, o2, [&] {
+    // (a call with too many frames is refused as such, by the shared check that follows)
+    return n_frames <= kMaxMatchFrames && (long long)n_frames * n_tpl >= (1ll << 31)
+               ? fail(KCMC_EUNSUPPORTED, "match_f32: n_frames * n_tpl too large")
+               : KCMC_OK;
+  });
 }
 
 // Layout of the two work areas of a float match.  The prepared part (template stats,
@@ -956,12 +941,10 @@ extern "C" int kcmc_match_frames_f32(kcmc_ctx* ctx, const float* des_tpl, const 
                                      int32_t* out_counts, kcmc_stream_t stream) {
   if (!ctx) return fail(KCMC_EINVAL, "kcmc_match_frames_f32: ctx is NULL");
   KCMC_TRY(check_f32_args(des_tpl, n_tpl, D, des_q, q_off, n_frames, max_nq, out_idx, out_dist));
-  if (n_frames > 0 && n_tpl > 0 && (!kp_tpl || !out_kp_ordered || !out_keep_bits || !out_counts || (max_nq > 0 && !kp_q)))
-    return fail(KCMC_EINVAL, "kcmc_match_frames_f32: NULL pointer");
-  if (n_tpl > 8192) return fail(KCMC_EUNSUPPORTED, "kcmc_match_frames_f32: n_tpl > 8192");
-  if (n_frames == 0 || n_tpl == 0) return KCMC_OK;
   hipStream_t s = (hipStream_t)stream;
-  KCMC_TRY(launch_knn_f32(ctx, des_tpl, n_tpl, D, des_q, q_off, n_frames, max_nq, out_idx, out_dist, s));
-  return launch_match_filter(out_idx, out_dist, kp_tpl, kp_q, q_off, n_frames, n_tpl, ratio, d_lo, d_hi,
-                             out_kp_ordered, out_keep_bits, out_counts, s);
+  return match_frames_tail(
+      "kcmc_match_frames_f32",
+      [&] { return launch_knn_f32(ctx, des_tpl, n_tpl, D, des_q, q_off, n_frames, max_nq, out_idx, out_dist, s); },
+      kp_tpl, kp_q, q_off, n_frames, n_tpl, max_nq, ratio, d_lo, d_hi, out_idx, out_dist, out_kp_ordered,
+      out_keep_bits, out_counts, s);
 }

@@ -18,7 +18,7 @@
 //   the key (bits << 21 | row) and the top-2 update (v_med3_u32, v_min_u32).
 #include <cfloat>
 
-#include "kcmc_internal.h"
+#include "match_common.h"
 
 namespace kcmc {
 namespace {
@@ -28,30 +28,12 @@ constexpr int kQChunk = 256;   // frame rows per LDS chunk (one row per thread w
 constexpr int kIdxBits = 21;   // frame rows < 2^21; the bit count (<= 512) sits above them
 constexpr uint32_t kNoKey = 0xffffffffu;
 
-__device__ __forceinline__ uint32_t med3_u32(uint32_t a, uint32_t b, uint32_t c) {
-  uint32_t r;
-  asm("v_med3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
-}
-
 // 4 descriptor bytes at column col, zero past D
 __device__ __forceinline__ uint32_t load4(const uint8_t* row, int col, int D) {
   uint32_t w = 0;
 #pragma unroll
   for (int b = 0; b < 4; ++b) w |= (col + b < D ? (uint32_t)row[col + b] : 0u) << (8 * b);
   return w;
-}
-
-__device__ __forceinline__ uint4 load16(const uint8_t* p) {
-  uint4 v;
-  __builtin_memcpy(&v, p, 16);  // global_load_dwordx4 (unaligned access is allowed for global memory)
-  return v;
-}
-
-// bytes of word w (0..3) of 16-byte piece k inside the descriptor
-__device__ __forceinline__ uint32_t byte_mask(int D, int k, int w) {
-  const int n = D - 16 * k - 4 * w;
-  return n >= 4 ? ~0u : (n <= 0 ? 0u : (1u << (8 * n)) - 1u);
 }
 
 template <int DP>
@@ -153,14 +135,10 @@ __global__ __launch_bounds__(kThreads) void knn2_hamming_kernel(const uint8_t* _
 
 int check_hamming_args(const void* des_tpl, int n_tpl, int D, const void* des_q, const void* q_off, int n_frames,
                        int max_nq, const void* o1, const void* o2) {
-  if (n_tpl < 0 || n_frames < 0 || max_nq < 0) return fail(KCMC_EINVAL, "match_hamming: negative size");
-  if (D < 1 || D > 64)
-    return fail(KCMC_EUNSUPPORTED, "match_hamming: descriptor length D must be in [1, 64] (got " + std::to_string(D) + ")");
-  if (max_nq >= (1 << kIdxBits)) return fail(KCMC_EUNSUPPORTED, "match_hamming: at most 2^21 - 1 rows per frame");
-  if (n_frames > 65535) return fail(KCMC_EUNSUPPORTED, "match_hamming: at most 65535 frames per call");
-  if (n_frames > 0 && n_tpl > 0 && (!des_tpl || !q_off || !o1 || !o2 || (max_nq > 0 && !des_q)))
-    return fail(KCMC_EINVAL, "match_hamming: NULL pointer");
-  return KCMC_OK;
+  return check_knn_args("match_hamming", 64, des_tpl, n_tpl, D, des_q, q_off, n_frames, max_nq, o1, o2, [&] {
+    return max_nq >= (1 << kIdxBits) ? fail(KCMC_EUNSUPPORTED, "match_hamming: at most 2^21 - 1 rows per frame")
+                                     : KCMC_OK;
+  });
 }
 
 int launch_knn_hamming(const uint8_t* des_tpl, int n_tpl, int D, const uint8_t* des_q, const int32_t* q_off,
@@ -199,12 +177,10 @@ extern "C" int kcmc_match_frames_hamming(kcmc_ctx* ctx, const uint8_t* des_tpl, 
                                          int32_t* out_counts, kcmc_stream_t stream) {
   if (!ctx) return fail(KCMC_EINVAL, "kcmc_match_frames_hamming: ctx is NULL");
   KCMC_TRY(check_hamming_args(des_tpl, n_tpl, D, des_q, q_off, n_frames, max_nq, out_idx, out_dist));
-  if (n_frames > 0 && n_tpl > 0 && (!kp_tpl || !out_kp_ordered || !out_keep_bits || !out_counts || (max_nq > 0 && !kp_q)))
-    return fail(KCMC_EINVAL, "kcmc_match_frames_hamming: NULL pointer");
-  if (n_tpl > 8192) return fail(KCMC_EUNSUPPORTED, "kcmc_match_frames_hamming: n_tpl > 8192");
-  if (n_frames == 0 || n_tpl == 0) return KCMC_OK;
   hipStream_t s = (hipStream_t)stream;
-  KCMC_TRY(launch_knn_hamming(des_tpl, n_tpl, D, des_q, q_off, n_frames, out_idx, out_dist, s));
-  return launch_match_filter(out_idx, out_dist, kp_tpl, kp_q, q_off, n_frames, n_tpl, ratio, d_lo, d_hi,
-                             out_kp_ordered, out_keep_bits, out_counts, s);
+  return match_frames_tail(
+      "kcmc_match_frames_hamming",
+      [&] { return launch_knn_hamming(des_tpl, n_tpl, D, des_q, q_off, n_frames, out_idx, out_dist, s); }, kp_tpl,
+      kp_q, q_off, n_frames, n_tpl, max_nq, ratio, d_lo, d_hi, out_idx, out_dist, out_kp_ordered, out_keep_bits,
+      out_counts, s);
 }

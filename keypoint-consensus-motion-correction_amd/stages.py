@@ -99,6 +99,23 @@ def _check_offsets(q_off_host: np.ndarray, n_frames: int) -> None:
         raise ValueError("q_off must be [F+1] non-decreasing CSR offsets starting at 0")
 
 
+def _knn(dev: torch.device, des_tpl: torch.Tensor, des_q: torch.Tensor, q_off: torch.Tensor, max_nq: int, norm: str,
+         stream: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The knn k=2 of checked arguments on ``stream``: idx / dist [F, n_tpl, 2] from the
+    float32, Hamming or uint8 L2 entry."""
+    n_tpl, D = des_tpl.shape
+    F = q_off.numel() - 1
+    with on_stream(dev, stream):  # the outputs belong to the stream that writes them
+        idx = torch.empty((F, n_tpl, 2), dtype=torch.int32, device=dev)
+        dist = torch.empty((F, n_tpl, 2), dtype=torch.float32, device=dev)
+    L = _lib.load()
+    fn = (L.kcmc_knn2_l2f32 if des_tpl.dtype == torch.float32 else
+          L.kcmc_knn2_hamming if norm == "hamming" else L.kcmc_knn2_l2u8)
+    _lib.check(fn(_ctx(dev).handle, _ptr(des_tpl), n_tpl, D, _ptr(des_q), _ptr(q_off), F, int(max_nq), _ptr(idx),
+                  _ptr(dist), _stream(dev, stream)))
+    return idx, dist
+
+
 def knn2_l2u8(des_tpl: torch.Tensor, des_q: torch.Tensor, q_off: torch.Tensor, max_nq: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """cv2.BFMatcher().knnMatch(des_tpl, des_q[frame], k=2) for every frame at once.
     uint8 descriptors (the reference's AKAZE/BRISK): exact integer distances, bit-exact
@@ -112,15 +129,7 @@ def knn2_l2u8(des_tpl: torch.Tensor, des_q: torch.Tensor, q_off: torch.Tensor, m
     _require(des_tpl, "des_tpl", torch.float32 if f32 else torch.uint8, dev, 2)
     _require(des_q, "des_q", torch.float32 if f32 else torch.uint8, dev, 2)
     _require(q_off, "q_off", torch.int32, dev, 1)
-    n_tpl, D = des_tpl.shape
-    F = q_off.numel() - 1
-    idx = torch.empty((F, n_tpl, 2), dtype=torch.int32, device=dev)
-    dist = torch.empty((F, n_tpl, 2), dtype=torch.float32, device=dev)
-    L = _lib.load()
-    fn = L.kcmc_knn2_l2f32 if f32 else L.kcmc_knn2_l2u8
-    _lib.check(fn(_ctx(dev).handle, _ptr(des_tpl), n_tpl, D, _ptr(des_q), _ptr(q_off), F, int(max_nq),
-                  _ptr(idx), _ptr(dist), _stream(dev)))
-    return idx, dist
+    return _knn(dev, des_tpl, des_q, q_off, max_nq, "l2")
 
 
 def knn2_hamming(des_tpl: torch.Tensor, des_q: torch.Tensor, q_off: torch.Tensor, max_nq: int) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -130,13 +139,7 @@ def knn2_hamming(des_tpl: torch.Tensor, des_q: torch.Tensor, q_off: torch.Tensor
     _require(des_tpl, "des_tpl", torch.uint8, dev, 2)
     _require(des_q, "des_q", torch.uint8, dev, 2)
     _require(q_off, "q_off", torch.int32, dev, 1)
-    n_tpl, D = des_tpl.shape
-    F = q_off.numel() - 1
-    idx = torch.empty((F, n_tpl, 2), dtype=torch.int32, device=dev)
-    dist = torch.empty((F, n_tpl, 2), dtype=torch.float32, device=dev)
-    _lib.check(_lib.load().kcmc_knn2_hamming(_ctx(dev).handle, _ptr(des_tpl), n_tpl, D, _ptr(des_q), _ptr(q_off), F,
-                                             int(max_nq), _ptr(idx), _ptr(dist), _stream(dev)))
-    return idx, dist
+    return _knn(dev, des_tpl, des_q, q_off, max_nq, "hamming")
 
 
 def match_frames(
@@ -209,15 +212,8 @@ def knn_frames(des_tpl: torch.Tensor, kp_tpl: torch.Tensor, des_q: torch.Tensor,
     """match_frames in two parts, the first: the knn k=2 of every frame (VA:194-195) on
     ``stream``, idx / dist [F, n_tpl, 2]; filter_matches finishes it (on another stream
     ordered after this one, if wanted).  Same checks and results as match_frames."""
-    dev, f32, n_tpl, D, F, max_nq = _match_args(des_tpl, kp_tpl, des_q, kp_q, q_off, q_off_host, norm)
-    with on_stream(dev, stream):  # the outputs belong to the stream that writes them
-        idx = torch.empty((F, n_tpl, 2), dtype=torch.int32, device=dev)
-        dist = torch.empty((F, n_tpl, 2), dtype=torch.float32, device=dev)
-    L = _lib.load()
-    fn = L.kcmc_knn2_l2f32 if f32 else (L.kcmc_knn2_hamming if norm == "hamming" else L.kcmc_knn2_l2u8)
-    _lib.check(fn(_ctx(dev).handle, _ptr(des_tpl), n_tpl, D, _ptr(des_q), _ptr(q_off), F, max_nq, _ptr(idx), _ptr(dist),
-                  _stream(dev, stream)))
-    return idx, dist
+    dev, *_, max_nq = _match_args(des_tpl, kp_tpl, des_q, kp_q, q_off, q_off_host, norm)
+    return _knn(dev, des_tpl, des_q, q_off, max_nq, norm, stream)
 
 
 def filter_matches(knn: Tuple[torch.Tensor, torch.Tensor], kp_tpl: torch.Tensor, kp_q: torch.Tensor,

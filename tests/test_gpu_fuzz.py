@@ -348,6 +348,14 @@ def test_match_filters_fuzz_vs_oracle(dev, seed):
         dist[f, :, 0], dist[f, :, 1] = d0, d1
         if n_tpl > 4:  # a few template points displaced exactly onto the 0.5x / 2x median boundaries
             kp_tpl[:2] = q[idx[f, :2, 0]]
+    _check_filters_vs_oracle(dev, idx, dist, kp_tpl, q_lists, seed)
+
+
+def _check_filters_vs_oracle(dev, idx, dist, kp_tpl, q_lists, tag):
+    """stages.filter_matches on knn results idx / dist [F, n_tpl, 2] against the oracle,
+    frame by frame: the kept set, kp_ordered bit for bit and the four counts.  Returns the
+    counts [F, 4] and the keep words [F, ceil(n_tpl / 32)]."""
+    n_tpl = idx.shape[1]
     off = _csr(q_lists)
     kq = np.concatenate(q_lists)
     res = stages.filter_matches((_t(idx, dev), _t(dist, dev)), _t(kp_tpl, dev), _t(kq, dev), _t(off, dev))
@@ -356,9 +364,58 @@ def test_match_filters_fuzz_vs_oracle(dev, seed):
     for f, q in enumerate(q_lists):
         s, kq_ref, c = oracle.filter_matches(idx[f], dist[f], kp_tpl, q)
         kept = [i for i in range(n_tpl) if (bits[f, i >> 5] >> (i & 31)) & 1]
-        assert kept == sorted(s), (seed, f, n_tpl)
-        assert np.array_equal(kqo[f], kq_ref), (seed, f)
-        assert cnt[f].tolist() == list(c), (seed, f)
+        assert kept == sorted(s), (tag, f, n_tpl)
+        assert np.array_equal(kqo[f], kq_ref), (tag, f)
+        assert cnt[f].tolist() == list(c), (tag, f)
+    return cnt, bits
+
+
+@pytest.mark.parametrize("n_tpl", [1, 63, 64, 65, 511, 512, 513, 1023, 4095, 4096, 4097, 8191, 8192])
+def test_match_filters_kernel_boundaries(dev, n_tpl):
+    """The filter kernel's three shapes at the edges of their template ranges (512, 4096,
+    8192), with the number of ratio survivors nr pinned per frame: 0 (nothing kept), 1,
+    16 (the median slots 7 and 8 in neighbouring lanes), 1024 (slots 511 and 512 in
+    neighbouring waves) and n_tpl, each clipped to n_tpl.  F = 5 leaves the one-wave
+    kernel's last workgroup partly empty.  The survivors are spread over the whole index
+    range, and where there are three or more, two of them sit exactly on the 0.5x and 2x
+    median band edges."""
+    rng = np.random.default_rng(5100 + n_tpl)
+    nrs = [min(nr, n_tpl) for nr in (0, 1, 16, 1024, n_tpl)]
+    F = len(nrs)
+    edge = (n_tpl // 2, n_tpl // 4)  # the template points of the band-edge survivors, at the origin
+    kp_tpl = rng.uniform(0, 500, (n_tpl, 2))
+    kp_tpl[list(edge)] = 0.0
+    q_lists = [rng.uniform(0, 500, (int(rng.integers(2, 301)), 2)) for _ in range(F)]
+    idx = np.zeros((F, n_tpl, 2), np.int32)
+    dist = np.zeros((F, n_tpl, 2), np.float32)
+    for f, (q, nr) in enumerate(zip(q_lists, nrs)):
+        idx[f] = rng.integers(0, len(q), (n_tpl, 2))
+        spread = (np.arange(nr) * n_tpl) // max(nr, 1)  # nr distinct rows from 0 up ...
+        if f & 1:
+            spread = n_tpl - 1 - spread                 # ... or from n_tpl - 1 down
+        on_edge = nr >= 3
+        if on_edge:
+            spread = np.concatenate([edge, [i for i in spread if i not in edge][:nr - 2]]).astype(np.int64)
+        assert len(set(spread.tolist())) == nr
+        d1 = rng.uniform(1, 300, n_tpl).astype(np.float32)
+        d0 = d1.copy()       # d0 == d1 fails the ratio test,
+        d0[spread] = 0       # 0 < 0.75 d1 passes it
+        dist[f, :, 0], dist[f, :, 1] = d0, d1
+        if on_edge:
+            # two survivors below / above the others' median leave it unchanged; from the
+            # origin to (t, 0) the displacement is exactly t (two query rows of their own)
+            others = spread[2:]
+            med = np.median(np.linalg.norm(kp_tpl[others] - q[idx[f, others, 0]], axis=1))
+            q = q_lists[f] = np.vstack([q, [(0.5 * med, 0.0), (2.0 * med, 0.0)]])
+            idx[f, edge[0], 0], idx[f, edge[1], 0] = len(q) - 2, len(q) - 1
+            d = np.linalg.norm(kp_tpl[spread] - q[idx[f, spread, 0]], axis=1)
+            assert np.median(d) == med and d[0] == 0.5 * med and d[1] == 2.0 * med
+    cnt, bits = _check_filters_vs_oracle(dev, idx, dist, kp_tpl, q_lists, "boundaries")
+    assert cnt[:, 2].tolist() == nrs
+    assert not bits[0].any() and cnt[0].tolist() == [n_tpl, n_tpl, 0, 0]
+    for f in range(F):
+        if nrs[f] >= 3:  # both band-edge survivors are kept (the band is closed)
+            assert all((bits[f, i >> 5] >> (i & 31)) & 1 for i in edge), (f, n_tpl)
 
 
 @pytest.mark.parametrize("seed", range(8))

@@ -154,6 +154,46 @@ def test_match_frames_rejects_frames_with_fewer_than_two_keypoints(dev):
                             _t(np.zeros((4, 2)), dev), _t(off, dev), off)
 
 
+def test_match_entries_argument_checks(dev):
+    """The return code and the exact kcmc_last_error() text of the argument checks of the
+    three kcmc_match_frames* entries and kcmc_match_filter.  Every call returns before
+    any launch (the pointers are never followed)."""
+    import ctypes
+
+    from kcmc_amd import _lib
+
+    L, ctx = _lib.load(), _lib.context(dev.index).handle
+    p = ctypes.c_void_p(torch.zeros(64, dtype=torch.uint8, device=dev).data_ptr())  # any non-NULL pointer
+    EINVAL, EUNSUP = _lib.KCMC_EINVAL, _lib.KCMC_EUNSUPPORTED
+
+    def frames(fn, n_tpl=8, D=32, n_frames=1, max_nq=4, out_idx=p, out_counts=p):
+        return fn(ctx, p, p, n_tpl, D, p, p, p, n_frames, max_nq, 0.75, 0.5, 2.0, out_idx, p, p, p, out_counts, None)
+
+    def filt(n_tpl=8, n_frames=1, out_counts=p):
+        return L.kcmc_match_filter(ctx, p, p, p, p, p, n_frames, n_tpl, 0.75, 0.5, 2.0, p, p, out_counts, None)
+
+    def expect(rc, code, text):
+        assert rc == code and L.kcmc_last_error().decode() == text, (rc, L.kcmc_last_error(), text)
+
+    for fn, entry, tag, d_max in ((L.kcmc_match_frames, "kcmc_match_frames", "match", 64),
+                                  (L.kcmc_match_frames_hamming, "kcmc_match_frames_hamming", "match_hamming", 64),
+                                  (L.kcmc_match_frames_f32, "kcmc_match_frames_f32", "match_f32", 128)):
+        expect(frames(fn, n_tpl=-1), EINVAL, f"{tag}: negative size")
+        expect(frames(fn, n_frames=-1), EINVAL, f"{tag}: negative size")
+        expect(frames(fn, max_nq=-1), EINVAL, f"{tag}: negative size")
+        for D in (0, d_max + 1):
+            expect(frames(fn, D=D), EUNSUP, f"{tag}: descriptor length D must be in [1, {d_max}] (got {D})")
+        expect(frames(fn, n_tpl=8193), EUNSUP, f"{entry}: n_tpl > 8192")
+        expect(frames(fn, out_idx=None), EINVAL, f"{tag}: NULL pointer")
+        expect(frames(fn, out_counts=None), EINVAL, f"{entry}: NULL pointer")
+        assert frames(fn, D=d_max, n_tpl=0) == _lib.KCMC_OK  # the largest D passes; nothing to do
+    expect(filt(n_tpl=-1), EINVAL, "kcmc_match_filter: negative size")
+    expect(filt(n_frames=-1), EINVAL, "kcmc_match_filter: negative size")
+    expect(filt(n_tpl=8193), EUNSUP, "kcmc_match_filter: n_tpl > 8192")
+    expect(filt(out_counts=None), EINVAL, "kcmc_match_filter: NULL pointer")
+    assert filt(n_tpl=0) == _lib.KCMC_OK
+
+
 # ------------------------------------------------------------------------ K2
 def _ransac(dev, tpls, qs, rate=1.0, trials=1000):
     off = _csr(qs)

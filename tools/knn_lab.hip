@@ -32,16 +32,17 @@ int workspace_alloc(kcmc_ctx*, void** p, size_t n, hipStream_t) {
   return 0;
 }
 int workspace_free(kcmc_ctx*, void*, hipStream_t, size_t) { return 0; }
-#ifdef KNN_F32  // match_f32.hip's kcmc_match_frames_f32 calls match.hip's filter launcher
+// the kcmc_match_frames* entries call match_filter.hip's filter launcher
+int launch_match_filter(const int32_t*, const float*, const double*, const double*, const int32_t*, int, int, double,
+                        double, double, double*, uint32_t*, int32_t*, hipStream_t) {
+  return KCMC_EUNSUPPORTED;
+}
+#ifdef KNN_F32  // match.hip's own otherwise
 int device_cus() {
   int d = 0, n = 256;
   (void)hipGetDevice(&d);
   (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d);
   return n;
-}
-int launch_match_filter(const int32_t*, const float*, const double*, const double*, const int32_t*, int, int, double,
-                        double, double, double*, uint32_t*, int32_t*, hipStream_t) {
-  return KCMC_EUNSUPPORTED;
 }
 #endif
 }  // namespace kcmc
@@ -62,7 +63,7 @@ typedef uint8_t Desc;
 static int launch(const Desc* t, int n_tpl, int D, const Desc* q, const int32_t* off, int F, int nq, int32_t* idx,
                   float* dist) {
 #ifdef KNN_F32
-  return kcmc::launch_knn_f32(nullptr, t, n_tpl, D, q, off, F, nq, nullptr, idx, dist, 0);
+  return kcmc::launch_knn_f32(nullptr, t, n_tpl, D, q, off, F, nq, idx, dist, 0);
 #else
   return kcmc::launch_knn(t, n_tpl, D, q, off, F, nq, idx, dist, 0);
 #endif
