@@ -121,8 +121,9 @@ __device__ __forceinline__ int sq2(uint32_t w, int acc) {
 // Chunk staging, one frame descriptor row per thread (row q0 + tid of a 256-row chunk):
 // 16-byte loads at offsets 0, 16, ... of the row (rows are not 16-byte aligned unless
 // D % 16 == 0; unaligned global loads are allowed), the last one running up to 15 bytes
-// into the next row (masked off when landing).  Only the very last row of des_q would run
-// past the buffer: its tail is read bytewise.  The loads of the next chunk are issued
+// into the next row (masked off when landing).  The rows at the end of des_q whose last
+// load would run past the buffer (staged_row_overruns: the last row, and for D <= 7 the few
+// before it) read that piece bytewise (load_row_pieces).  The loads of the next chunk are issued
 // before the current chunk's MFMA tiles so that their latency hides behind them.
 // Landing turns them into the padded int8 row (127 - b, zero past D), its key part
 // (Q + B) << 8 | row and the LDS writes, all in registers.
@@ -130,24 +131,6 @@ template <int DP>
 struct RowPieces {
   static constexpr int kNP = DP / 16;
 };
-
-template <int DP>
-__device__ __forceinline__ void issue_row(const uint8_t* __restrict__ row, int D, bool last_row,
-                                          uint4 (&pf)[RowPieces<DP>::kNP]) {
-  constexpr int NP = RowPieces<DP>::kNP;
-  const int np = (D + 15) >> 4;  // pieces holding the row (uniform)
-#pragma unroll
-  for (int k = 0; k < NP; ++k) pf[k] = load16(row + 16 * min(k, np - 1));
-  if (last_row && (D & 15) != 0) {  // one lane in the whole grid: no read past des_q
-    uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int c = 0; c < 16; ++c)
-      if (16 * (np - 1) + c < D) w[c >> 2] |= (uint32_t)row[16 * (np - 1) + c] << (8 * (c & 3));
-#pragma unroll
-    for (int k = 0; k < NP; ++k)  // (a register array is never indexed at run time)
-      if (k == np - 1) pf[k] = make_uint4(w[0], w[1], w[2], w[3]);
-  }
-}
 
 template <int DP>
 __device__ __forceinline__ void land_row(uint8_t* qrow, uint32_t* qk, int r, bool real, int D,
@@ -239,7 +222,7 @@ __global__ __launch_bounds__(KnnShape<WAVES>::kThreads) void knn2_l2u8_kernel(
     if (it.x < n_frames && tid < kQChunk) {
       const int qb = q_off[it.x], nq = q_off[it.x + 1] - qb;
       const int r = qb + it.y + min(tid, nq - it.y - 1);
-      issue_row<DP>(des_q + (size_t)r * D, D, r == last_global, pf);
+      load_row_pieces(des_q + (size_t)r * D, D, staged_row_overruns(D, last_global - r), pf);
     }
   };
   uint4 pf[RowPieces<DP>::kNP];
@@ -338,7 +321,8 @@ __global__ __launch_bounds__(KnnShape<WAVES>::kThreads) void knn2_l2u8_kernel(
 
 // persistent grid: n_tg template groups x G frame strides, G = the resident workgroups
 // per template group (workgroups never wait on each other, so a wrong residency count
-// costs balance, not progress)
+// costs balance, not progress).  tests/test_gpu_matcher_paths.py sizes its frame counts by
+// the bound G <= 8 * CUs / n_tg (2048 threads per CU): a policy past it moves that bound too.
 int knn_grid(int n_tg, int n_frames, int wgs_per_cu) {
   const int G = std::max(1, std::min(n_frames, device_cus() * std::max(1, wgs_per_cu) / n_tg));
   return n_tg * G;

@@ -57,22 +57,13 @@ __global__ __launch_bounds__(kThreads) void knn2_hamming_kernel(const uint8_t* _
   for (int k = 0; k < DW; ++k) tw[k] = i < n_tpl ? load4(des_tpl + (size_t)i * D, 4 * k, D) : 0u;
 
   // staging: thread tid loads frame row q0 + tid as NP 16-byte pieces (the last one may
-  // run into the next row; masked when landing); des_q's very last row is read bytewise
+  // run into the next row; masked when landing); the rows at des_q's end whose last load
+  // would run past the buffer read that piece bytewise (staged_row_overruns)
   uint4 pf[NP];
   auto issue = [&](int qb, int nq, int q0) {
     const int r = qb + q0 + min(tid, nq - q0 - 1);
     const uint8_t* row = des_q + (size_t)r * D;
-    const int np = (D + 15) >> 4;
-#pragma unroll
-    for (int k = 0; k < NP; ++k) pf[k] = load16(row + 16 * min(k, np - 1));
-    if (r == last_global && (D & 15) != 0) {  // one lane in the grid: no read past des_q
-      uint32_t w[4] = {0u, 0u, 0u, 0u};
-      for (int cc = 0; cc < 16; ++cc)
-        if (16 * (np - 1) + cc < D) w[cc >> 2] |= (uint32_t)row[16 * (np - 1) + cc] << (8 * (cc & 3));
-#pragma unroll
-      for (int k = 0; k < NP; ++k)
-        if (k == np - 1) pf[k] = make_uint4(w[0], w[1], w[2], w[3]);
-    }
+    load_row_pieces(row, D, staged_row_overruns(D, last_global - r), pf);
   };
   auto next_frame = [&](int f) {
     for (f += G; f < n_frames && q_off[f + 1] == q_off[f]; f += G) {
@@ -146,7 +137,8 @@ int launch_knn_hamming(const uint8_t* des_tpl, int n_tpl, int D, const uint8_t* 
   if (n_frames == 0 || n_tpl == 0) return KCMC_OK;
   const int cus = device_cus();
   const int n_tg = ceil_div(n_tpl, kThreads);
-  // workgroups per CU: LDS-bound (2 x 256 rows x 32 / 64 B per workgroup)
+  // workgroups per CU: LDS-bound (2 x 256 rows x 32 / 64 B per workgroup).
+  // tests/test_gpu_matcher_paths.py sizes its frame counts by G <= 8 * CUs / n_tg.
   const int G = std::max(1, std::min(n_frames, (D <= 32 ? 8 : 4) * cus / n_tg));
   if (D <= 32)
     hipLaunchKernelGGL(knn2_hamming_kernel<32>, dim3(n_tg * G), dim3(kThreads), 0, s, des_tpl, n_tpl, D, des_q, q_off,

@@ -166,7 +166,7 @@ def test_config4_4k_rgb_affine_slab(dev):
 
 def test_config5_float_matcher_4096x128(dev):
     """c5's matcher shape: 4096 float32 template descriptors x ~4500 per frame, D = 128
-    (bf16x3 MFMA candidates + exact fp64 re-rank), bit-exact indices and distances."""
+    (fp16 MFMA top-8 candidates + exact fp64 re-rank), bit-exact indices and distances."""
     F = 4
     ks = synthetic.make_keypoints(F, 4096, 128, (1080, 1920), seed=47, model="projective", descriptor="f32")
     idx, dist = stages.knn2_l2u8(_t(ks.des_tpl, dev), _t(ks.des_q, dev), _t(ks.q_off, dev),

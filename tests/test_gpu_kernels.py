@@ -184,6 +184,8 @@ def test_match_entries_argument_checks(dev):
         for D in (0, d_max + 1):
             expect(frames(fn, D=D), EUNSUP, f"{tag}: descriptor length D must be in [1, {d_max}] (got {D})")
         expect(frames(fn, n_tpl=8193), EUNSUP, f"{entry}: n_tpl > 8192")
+        expect(frames(fn, n_frames=65536), EUNSUP, f"{tag}: at most 65535 frames per call")
+        assert frames(fn, n_frames=65535, n_tpl=0) == _lib.KCMC_OK  # the largest count passes; nothing to do
         expect(frames(fn, out_idx=None), EINVAL, f"{tag}: NULL pointer")
         expect(frames(fn, out_counts=None), EINVAL, f"{entry}: NULL pointer")
         assert frames(fn, D=d_max, n_tpl=0) == _lib.KCMC_OK  # the largest D passes; nothing to do

@@ -283,9 +283,12 @@ def test_video_aligner_model_selector(dev):
 # ------------------------------------------------------------ float descriptors (K1f)
 @pytest.mark.parametrize("D", [1, 3, 64, 100, 128])
 def test_knn2_f32_matches_oracle(dev, D):
-    """MFMA candidate search + exact re-ranking == exact brute force (indices and
-    distances bit-exact), including exact duplicates (ties -> lower index) and runs of
-    4+ equidistant rows, which take the exact fallback path."""
+    """fp16 MFMA candidate search (top-8 per row) + exact re-ranking == exact brute force
+    (indices and distances bit-exact) over frame sizes 0..1500 and D = 1..128, including
+    exact duplicates and five copies of one template row (ties -> lower index).  Five
+    equidistant rows fit the top-8 and are re-ranked in place: this test does not force
+    the exact fallback (at D = 1 or 3 rows may reach it by chance);
+    tests/test_gpu_matcher_paths.py does, with 8+ identical rows."""
     rng = np.random.default_rng(100 + D)
     n_tpl = 300
     tpl = rng.normal(0, 1, (n_tpl, D)).astype(np.float32)
@@ -309,9 +312,12 @@ def test_knn2_f32_matches_oracle(dev, D):
 
 @pytest.mark.parametrize("scale", [1e-3, 37.0, 1e4])
 def test_knn2_f32_scaled_and_near_ties(dev, scale):
-    """The bf16x3 candidate search's error bound scales with the descriptor norms: scaled
-    descriptors, frame rows that differ from a template row by one bf16 ulp of a single
-    element (near-ties below the split's resolution) and rows of mixed magnitude."""
+    """The fp16 candidate search's error bound scales with the descriptor norms: scaled
+    descriptors, twelve frame rows that differ from a template row by one fp32 ulp of a
+    single element (near-ties far below fp16's resolution: more of them than the top-8
+    holds, so that template row cannot be certified and is finished by the exact fallback)
+    and rows of mixed magnitude.  Guaranteed: bit-exact indices and distances at every
+    scale; the fallback's batching and grid-strides are tests/test_gpu_matcher_paths.py's."""
     rng = np.random.default_rng(int(scale * 10))
     n_tpl, D = 200, 128
     tpl = (rng.normal(0, 1, (n_tpl, D)) * scale).astype(np.float32)
