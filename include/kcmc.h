@@ -31,6 +31,9 @@
  *   kcmc_gradient_sums_u16 <- nothing in the reference (an extension): the right-hand side
  *                             of one least-squares step of every frame against the mean
  *                             image, for the intensity refinement of the frames' maps.
+ *   kcmc_tile_gradient_sums_u16 <- nothing in the reference (an extension): the same
+ *                             right-hand side on every patch of a tiling from one read of
+ *                             the stack, for the non-rigid intensity refinement.
  *
  * Conventions
  *   - Plain pointers and sizes only.  Pointers named *_dev are device (HBM) pointers
@@ -539,6 +542,49 @@ int kcmc_shift_search_u16(kcmc_ctx* ctx, const uint16_t* frames_dev, int n_frame
 int kcmc_gradient_sums_u16(kcmc_ctx* ctx, const uint16_t* frames_dev, int n_frames, int H, int W,
                            const int32_t* frame_idx_dev, int n_sel, const uint16_t* ref_dev, int y0, int y1,
                            int x0, int x1, int band_rows, long long* out_dev, kcmc_stream_t stream);
+
+/* ----------------------------- g2: gradient sums per tile (non-rigid intensity refinement)
+ * Build-defined: the reference has no dense step and no non-rigid mode.
+ *
+ * g1's right-hand side on every patch of a tiling, from one read of the stack: the translation
+ * part of g1's model, a ~ alpha b + beta + qx gx + qy gy with the same integer gradients gx, gy of
+ * b (twice the central difference), fitted per patch (host, kcmc_amd.refine_field) gives a
+ * displacement per grid node instead of one per frame.
+ *
+ * row_edges_host [ty + 1], col_edges_host [tx + 1] i32, HOST arrays (as level_h of
+ * kcmc_orb_detect_pyramid), non-decreasing: tile (i, j) is the rows [row_edges[i],
+ * row_edges[i + 1]) and the columns [col_edges[j], col_edges[j + 1]).  They are read and
+ * validated before any device work and handed to the kernel by value: no upload, no
+ * synchronisation, and the call can be captured into a graph.
+ *
+ * out_dev [n_sel, ty, tx, 5] i64: entry [s][i][j] = (sum a, sum a^2, sum a b, sum a gx, sum a gy)
+ * over tile (i, j), a = frames_dev[frame_idx_dev[s]] (frames_dev [n_frames, H, W] u16),
+ * b = ref_dev [H, W] u16; a, b, gx, gy exactly as in kcmc_gradient_sums_u16, so the sum over all
+ * tiles equals the first five of its sums over the rectangle [row_edges[0], row_edges[ty]) x
+ * [col_edges[0], col_edges[tx]).  A tile without pixels (two equal edges) gives zeros.  Pixels
+ * outside the tiling contribute nothing as a; as b they are read where the gradient at the
+ * tiling's edge needs them.
+ *
+ * frame_idx_dev [n_sel] i32; NULL = frames 0 .. n_sel - 1.  An index outside [0, n_frames)
+ * gives all-zero rows and is never read through; repeated and unordered indices are fine.
+ *
+ * Contract (KCMC_EINVAL before any device work otherwise, as for a NULL ctx or pointer):
+ * 1 <= ty, tx <= 32, both edge lists non-decreasing, 1 <= row_edges[0], row_edges[ty] <= H - 1,
+ * 1 <= col_edges[0], col_edges[tx] <= W - 1 (the gradient reads +-1), H * W < 2^31, out_dev 8-byte
+ * aligned.  n_sel == 0 is KCMC_OK; KCMC_EUNSUPPORTED when n_sel * ty >= 2^31.  Any alignment of
+ * frames_dev / ref_dev and any W: the 16-byte path needs W % 8 == 0 and 16-byte aligned
+ * frames_dev and ref_dev, everything else is read element by element.
+ *
+ * Exact: every value is a signed 64-bit integer (no floating point).  A tile has fewer than
+ * 2^31 pixels and every product a^2, a b, a g is below 2^32 in magnitude, so no tile sum can
+ * reach 2^63; there are no coordinate moments, so no bands.  One workgroup owns each (frame,
+ * tile row), adds its threads' integer partial sums in LDS and writes its tx entries with
+ * plain stores, so nothing depends on the order in which workgroups or waves finish.
+ * Asynchronous on `stream`, no allocation, no memset: every entry of out_dev is written. */
+int kcmc_tile_gradient_sums_u16(kcmc_ctx* ctx, const uint16_t* frames_dev, int n_frames, int H, int W,
+                                const int32_t* frame_idx_dev, int n_sel, const uint16_t* ref_dev,
+                                const int32_t* row_edges_host, int ty, const int32_t* col_edges_host, int tx,
+                                long long* out_dev, kcmc_stream_t stream);
 
 #ifdef __cplusplus
 }

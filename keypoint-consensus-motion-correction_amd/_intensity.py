@@ -61,7 +61,8 @@ def sample_mask(n_images: int, rate: int, skipped) -> np.ndarray:
 
 def run_indexed(fn, parts, idx: np.ndarray, ref, rect: Region, trailing: tuple, tail: tuple):
     """The C entry point ``fn`` (kcmc_shift_search_u16, kcmc_gradient_sums_u16: ``trailing`` its
-    arguments between the rectangle and the output) once per slab, over the frames ``idx`` (int64
+    arguments between the rectangle and the output; kcmc_tile_gradient_sums_u16: ``rect`` empty, the
+    tile edges and their counts in ``trailing``) once per slab, over the frames ``idx`` (int64
     global indices, any order, repeats allowed) that lie in the slab.  Returns per call (rows, out):
     out the slab's device tensor [len(rows), *tail] int64, rows the positions in ``idx`` it answers;
     an index outside the stack is in no rows.  The calls are queued on every device before the

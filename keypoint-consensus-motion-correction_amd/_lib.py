@@ -62,6 +62,7 @@ EXPORTED_SYMBOLS = (
     "kcmc_frame_stats_u16",
     "kcmc_shift_search_u16",
     "kcmc_gradient_sums_u16",
+    "kcmc_tile_gradient_sums_u16",
 )
 
 KCMC_MODEL_EUCLIDEAN = 0
@@ -134,6 +135,7 @@ _SIGNATURES = {
     "kcmc_frame_stats_u16": ([P, P, I, I, I, P, I, I, I, I, P, P], I),
     "kcmc_shift_search_u16": ([P, P, I, I, I, P, I, P, I, I, I, I, I, P, P], I),
     "kcmc_gradient_sums_u16": ([P, P, I, I, I, P, I, P, I, I, I, I, I, P, P], I),
+    "kcmc_tile_gradient_sums_u16": ([P, P, I, I, I, P, I, P, P, I, P, I, P, P], I),
 }
 
 

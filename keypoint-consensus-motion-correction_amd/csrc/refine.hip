@@ -163,22 +163,7 @@ extern "C" int kcmc_gradient_sums_u16(kcmc_ctx* ctx, const uint16_t* frames, int
   if (blocks > 0x7fffffffll) return fail(KCMC_EUNSUPPORTED, "kcmc_gradient_sums_u16: n_sel * n_bands too large");
 
   const bool vec = rows_vectorizable(W, frames, ref);
-  // thread columns: the largest power of two in [8, 256] that idles at most 1/8 of them over
-  // the row's vectors, else the one that idles fewest
-  const int nvec = (x1 + 7) / 8 - x0 / 8;
-  int ct_log2 = 3;
-  long long best = -1;
-  for (int l = 8; l >= 3; --l) {
-    const long long ct = 1ll << l, used = (nvec + ct - 1) / ct * ct;
-    if (used * 8 <= (long long)nvec * 9) {
-      ct_log2 = l;
-      break;
-    }
-    if (best < 0 || used < best) {
-      best = used;
-      ct_log2 = l;
-    }
-  }
+  const int ct_log2 = thread_columns_log2((x1 + 7) / 8 - x0 / 8);
   auto* o = reinterpret_cast<unsigned long long*>(out);
   const dim3 grid((unsigned)blocks), block(kThreads);
   if (vec)

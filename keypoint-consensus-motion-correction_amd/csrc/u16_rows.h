@@ -1,5 +1,6 @@
 // Rows of uint16 pixels as 16-byte vectors of eight, and what the exact-integer passes over
-// a uint16 stack share around them: quality.hip (q1), shift_search.hip (s1), refine.hip (g1).
+// a uint16 stack share around them: quality.hip (q1), shift_search.hip (s1), refine.hip (g1),
+// refine_tiles.hip (g2).
 #pragma once
 
 #include "kcmc_internal.h"
@@ -85,6 +86,23 @@ int launch_copy_b(u64* out, size_t n_entries, int group, hipStream_t s);
 int check_rect(const char* fn, kcmc_ctx* ctx, int n_frames, int n_sel, int H, int W, int y0, int y1, int x0, int x1,
                int margin, const char* grown);
 int check_pointers(const char* fn, const void* frames, int n_frames, const void* ref, const void* out);
+
+// log2 of the thread columns of a 256-thread workgroup that walks rows of nvec 8-pixel vectors
+// (g1, g2): the largest power of two in [8, 256] that idles at most 1/8 of the thread columns
+// over the row's vectors, else the one that idles fewest.
+inline int thread_columns_log2(int nvec) {
+  int ct_log2 = 3;
+  long long best = -1;
+  for (int l = 8; l >= 3; --l) {
+    const long long ct = 1ll << l, used = (nvec + ct - 1) / ct * ct;
+    if (used * 8 <= (long long)nvec * 9) return l;
+    if (best < 0 || used < best) {
+      best = used;
+      ct_log2 = l;
+    }
+  }
+  return ct_log2;
+}
 
 // Whether every row of the frames and of ref starts on a 16-byte boundary.
 inline bool rows_vectorizable(int W, const void* frames, const void* ref) {

@@ -37,6 +37,7 @@ from . import piecewise as _pw
 from . import pipeline as _pl
 from . import quality as _q
 from . import refine as _rf
+from . import refine_field as _rff
 from . import stages
 from .affines import AlignmentError
 
@@ -197,6 +198,19 @@ class VideoAligner:
     REFINE_ITERS = 2
     REFINE_MOTION = "rigid"         # or "translation"
     REFINE_MAX_STEP = 1.0           # px
+    # New (opt-in, kcmc_amd.refine_field; build-defined): the non-rigid step after that one,
+    # with REFINE = "intensity" only.  (gy, gx), each in [1, 16]: REFINE_GRID_ITERS times, every
+    # frame takes the same least-squares step (gain, offset, translation) on a window around
+    # every node of the grid -- the node's cell and half a cell to each side -- from five exact
+    # integer sums per tile of one read of the aligned stack (csrc/refine_tiles.hip), over the
+    # valid region shrunk by ceil(REFINE_GRID_ITERS * REFINE_MAX_STEP); a node's step is
+    # limited to REFINE_MAX_STEP px, added to the frame's field, the frame is made again from
+    # its source by the field warp, and the field is kept only where the frame's correlation
+    # with the mean image rose.  affines, the transform summary, skipped_idxs and
+    # interpolated_idxs stay what they are.  Results: refine_field, refine_field_correlations,
+    # refine_field_idxs.  Not with QUALITY_METRICS / TEMPLATE_REFINE_ITERS.
+    REFINE_GRID: Optional[Tuple[int, int]] = None
+    REFINE_GRID_ITERS = 1
 
     def __init__(self, logger: LoggerAdapter = None):
         self.logger = logger
@@ -342,10 +356,28 @@ class VideoAligner:
         self.refine_steps = None
         self.refine_correlations = None
         self.refine_idxs = None
+        self.refine_field = None
+        self.refine_field_correlations = None
+        self.refine_field_idxs = None
+
+    def _refine_grid_on(self) -> bool:
+        """Whether the field stage follows the refinement, after the checks of its own switches."""
+        if self.REFINE_GRID is None:
+            return False
+        if self.REFINE == "none":
+            raise ValueError("REFINE_GRID needs REFINE = 'intensity' (the field stage runs after the refinement "
+                             "of the frames' maps)")
+        _rff.check_grid(self.REFINE_GRID)
+        _rff.check_iters(self.REFINE_GRID_ITERS)
+        if bool(self.QUALITY_METRICS) or int(self.TEMPLATE_REFINE_ITERS) > 0:
+            raise NotImplementedError("REFINE_GRID does not run together with QUALITY_METRICS / "
+                                      "TEMPLATE_REFINE_ITERS (their valid region is the affine maps')")
+        return True
 
     def _refine_on(self, images=None) -> bool:
         """Whether the intensity refinement runs, after the checks that must fail before any
         work (``images``: only its number of dimensions is read, when it has one)."""
+        self._refine_grid_on()
         if self.REFINE == "none":
             return False
         if self.REFINE != "intensity":
@@ -370,6 +402,12 @@ class VideoAligner:
                                    logger=self.logger)
             self.refine_steps, self.refine_correlations, self.refine_idxs = rf.steps, rf.correlations, rf.idxs
             self.affines = res.affines
+            if self._refine_grid_on():
+                ff = _rff.refine_field_frames(res, [inp.frames for inp in slabs], n_images, rate, self.REFINE_GRID,
+                                              int(self.REFINE_GRID_ITERS), float(self.REFINE_MAX_STEP),
+                                              logger=self.logger)
+                self.refine_field, self.refine_field_correlations = ff.field, ff.correlations
+                self.refine_field_idxs = ff.idxs
             return res
 
         return refined
