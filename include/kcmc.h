@@ -22,6 +22,8 @@
  *                             reference fits EuclideanTransform only).
  *   kcmc_warp_affine_u16   <- _apply_affine (VA:455-458): cv2.warpAffine(img, M, (W,H),
  *                             INTER_LINEAR), BORDER_CONSTANT 0, classic fixed-point path.
+ *   kcmc_warp_affine_cubic_u16 <- nothing in the reference (an extension): the same warp
+ *                             with OpenCV's classic INTER_CUBIC restated, grayscale.
  *   kcmc_stack_sum_u16 / kcmc_frame_stats_u16  <- nothing in the reference (an extension):
  *                             the mean image of the aligned stack and every frame's
  *                             correlation moments with it.
@@ -365,6 +367,43 @@ int kcmc_warp_perspective_u16(kcmc_ctx* ctx, const uint16_t* src_dev, uint16_t* 
 int kcmc_warp_field_u16(kcmc_ctx* ctx, const uint16_t* src_dev, uint16_t* dst_dev, const double* M_dev,
                         const int32_t* field_dev, int n_frames, int H, int W, int gy, int gx,
                         int inverse_map, kcmc_stream_t stream);
+
+/* K3c: bicubic warpAffine of grayscale frames -- kcmc_warp_affine_u16 with INTER_CUBIC in place
+ * of INTER_LINEAR.  The reference never resamples cubically: the semantics are BUILD-DEFINED, a
+ * restatement of OpenCV's classic algorithm (WarpAffineInvoker + remapBicubic<Cast<float,
+ * ushort>, float, 1>, BORDER_CONSTANT 0) pinned by a numpy restatement
+ * (tests/test_warp_cubic_host.py); PARITY WITH cv2 IS UNPINNED.  For output pixel (x, y) of a
+ * frame with 2 x 3 map M (forward, or inverse with inverse_map != 0):
+ *   1. Coordinates: exactly kcmc_warp_affine_u16's -- the same inversion, the same cvRounds,
+ *      the same + 16, X and Y in 1/1024 px; sx = sat_short(X >> 10), fx = (X >> 5) & 31,
+ *      likewise sy, fy.  A frame whose map holds a NaN is zeros.
+ *   2. 1-D weights: the cubic-convolution kernel with A = -3/4 at t = f / 32,
+ *        c0 = ((A (t + 1) - 5A)(t + 1) + 8A)(t + 1) - 4A
+ *        c1 = ((A + 2) t - (A + 3)) t^2 + 1
+ *        c2 = ((A + 2)(1 - t) - (A + 3))(1 - t)^2 + 1
+ *        c3 = 1 - c0 - c1 - c2
+ *      OpenCV evaluates them in float32; for all 32 fractions every intermediate is exact and
+ *      each weight is an integer multiple of 2^-17 (f = 0: [0, 1, 0, 0]; f = 16:
+ *      [-3, 19, 19, -3] / 32; f = 1: [-2883, 130789, 3259, -93] / 2^17).
+ *   3. 2-D weights: w[i][j] = fl32(c_i(fy) c_j(fx)), one float32 rounding of the exact product
+ *      (OpenCV's BicubicTab_f entry).
+ *   4. Taps S[sy - 1 + i][sx - 1 + j], i, j = 0..3, as float32; a tap outside the image reads
+ *      0.  Every product p_ij = fl32(S w) and every sum is a separate float32 operation (no FMA
+ *      contraction).
+ *        interior pixel (0 <= sx - 1, sx + 2 <= W - 1, the same in y; never when W or H < 4):
+ *          r_i = ((p_i0 + p_i1) + p_i2) + p_i3,  sum = ((r_0 + r_1) + r_2) + r_3
+ *        any other pixel: sum = 0, then sum = sum + p_ij for i = 0..3 and within that j = 0..3
+ *   5. Output: saturate_cast<ushort>(sum) -- rintf, then a clamp to [0, 65535]; the negative
+ *      lobes make the clamp reachable on both sides.
+ * So an identity map returns the source bit for bit and an integer shift is a copy with zeros
+ * shifted in.  Arguments and limits as kcmc_warp_affine_u16 (H, W < 32768, at most 65535 frames,
+ * in-place refused), except: a NULL ctx or pointer and H or W < 1 return KCMC_EINVAL before any
+ * device work, n_frames == 0 returns KCMC_OK, C == 3 or 4 return KCMC_EUNSUPPORTED (grayscale
+ * only in this version) and any other C != 1 KCMC_EINVAL.  Asynchronous on `stream`, capturable
+ * under the affine warp's workspace rules. */
+int kcmc_warp_affine_cubic_u16(kcmc_ctx* ctx, const uint16_t* src_dev, uint16_t* dst_dev,
+                               const double* M_dev, int n_frames, int H, int W, int C,
+                               int inverse_map, kcmc_stream_t stream);
 
 /* ------------------------------------------- f2: normalisation front end (VA:100-104)
  * brightest = np.percentile(images, 99.99) (VA:479-482) needs two order statistics of

@@ -93,6 +93,28 @@ HIP_STAGES = SlabStages(_hip_match, _hip_vote, _hip_lookup, _hip_ransac, stages.
                         _hip_warp_params)
 
 
+def stages_for(cfg: _pl.AlignConfig, impl: SlabStages, where: str, frames_dim: Optional[int] = None) -> SlabStages:
+    """``impl`` with cfg.warp_interpolation honoured: the HIP stage table's warp and warp_params
+    are replaced by their bicubic forms; another table's warps take no interpolation, so the
+    switch is refused there instead of ignored."""
+    import dataclasses
+
+    interp = _pl.check_warp_interpolation(cfg, frames_dim)
+    if interp == "linear":
+        return impl
+    if impl.warp is not _hip_warp or impl.warp_params not in (None, _hip_warp_params):
+        raise NotImplementedError(f"warp_interpolation={interp!r} is not supported by {where} with a custom "
+                                  "stage table (its warps take no interpolation)")
+
+    def warp(frames: torch.Tensor, affines: np.ndarray) -> torch.Tensor:
+        return _pl.warp_stage(frames, affines, interpolation=interp)
+
+    def warp_params(frames: torch.Tensor, params: torch.Tensor) -> torch.Tensor:
+        return _pl.warp_frames(frames, params, interpolation=interp)
+
+    return dataclasses.replace(impl, warp=warp, warp_params=None if impl.warp_params is None else warp_params)
+
+
 def _all_gather_rows(t: torch.Tensor, counts: List[int], group=None) -> torch.Tensor:
     """All-gather a [F_r, ...] tensor whose first dimension differs per rank."""
     world = dist.get_world_size(group)
@@ -156,6 +178,7 @@ def align_sharded(inp: _pl.SlabInputs, cfg: _pl.AlignConfig, group=None, impl: S
     if cfg.frame_downsample_rate != 1:
         raise ValueError("the sharded path requires frame_downsample_rate == 1 (frame_rate < 2*FRAME_SAMPLE_RATE)")
     _pl.refuse_piecewise(cfg, "align_sharded")
+    impl = stages_for(cfg, impl, "align_sharded", inp.frames.dim())
     rank = dist.get_rank(group)
     dev = inp.kp_tpl.device
     n_local = inp.q_off.numel() - 1

@@ -32,7 +32,7 @@ from . import _lib
 from . import quality as _q
 from ._intensity import Frames, Region
 from .pipeline import summary_transforms
-from .stages import warp_affine_u16
+from .stages import check_interpolation, warp_affine_u16
 
 MAX_RADIUS = 16
 
@@ -143,12 +143,15 @@ class FallbackResult:
 
 def correct_skipped(res, sources: Sequence[torch.Tensor], n_images: int, rate: int, model: str, radius: int,
                     min_corr: float = 0.0, subpixel: bool = True,
-                    logger: Optional[logging.Logger] = None) -> FallbackResult:
+                    logger: Optional[logging.Logger] = None, interpolation: str = "linear") -> FallbackResult:
     """The pass over one result of the hot path (``res``: a SlabResult or SplitResult whose
     aligned frames are still on their devices; ``sources``: each slab's source frames).
     Changes ``res`` in place: the accepted frames' rows of the aligned stack, of ``affines``
-    and of the transform summary.  ``res.skipped`` / ``res.interpolated`` stay what they are."""
+    and of the transform summary.  ``res.skipped`` / ``res.interpolated`` stay what they are.
+    ``interpolation``: the warp's ("linear" or "cubic"); the frames are warped again with it and
+    the valid region is the one of its footprint."""
     R = check_radius(radius)
+    taps = 4 if check_interpolation(interpolation) == "cubic" else 2
     parts = _in.pass_parts("correlation fallback", res)
     H, W = parts[0].shape[1:]
     skipped = [int(i) for i in res.skipped if 0 <= int(i) < n_images]
@@ -159,7 +162,7 @@ def correct_skipped(res, sources: Sequence[torch.Tensor], n_images: int, rate: i
     info = logger.info if logger is not None else (lambda msg: None)
     try:
         ref = _q.mean_image(parts, _in.sample_mask(n_images, rate, skipped))
-        rect = search_region(_q.valid_region(np.asarray(res.affines)[:n_images], H, W), R)
+        rect = search_region(_q.valid_region(np.asarray(res.affines)[:n_images], H, W, taps=taps), R)
     except ValueError as e:
         info(f"correlation fallback: nothing corrected ({e})")
         return out
@@ -181,7 +184,7 @@ def correct_skipped(res, sources: Sequence[torch.Tensor], n_images: int, rate: i
     # the accepted frames again, from their source frames, into their rows of the aligned stack
     for src, dst, f0, a, b in _in.rewarp_runs(sources, parts, out.idxs):
         maps = torch.from_numpy(np.stack([new_maps[f0 + j] for j in range(a, b)])).to(dst.device)
-        warp_affine_u16(src[a:b], maps, out=dst[a:b])
+        warp_affine_u16(src[a:b], maps, out=dst[a:b], interpolation=interpolation)
     for i in out.idxs:
         res.affines[i] = new_maps[i]
         res.euclidean[i] = summary_transforms(new_maps[i][None], model)[0]

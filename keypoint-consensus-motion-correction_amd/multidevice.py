@@ -117,7 +117,9 @@ def align_split(slabs: Sequence[_pl.SlabInputs], ranges: Sequence[SlabRange], cf
     if len(slabs) != len(ranges) or not slabs:
         raise ValueError("align_split: one SlabRange per slab, at least one slab")
     _pl.refuse_piecewise(cfg, "align_split")
-    impl = impl or _hip_stages()
+    from . import distributed as kdist
+
+    impl = kdist.stages_for(cfg, impl or _hip_stages(), "align_split", slabs[0].frames.dim())
     n_tpl = slabs[0].des_tpl.shape[0]
     n_sample = ranges[-1].s1
     # 1. match + vote of every slab, queued on every device before the host waits

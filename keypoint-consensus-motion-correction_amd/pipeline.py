@@ -51,6 +51,10 @@ class AlignConfig:
     piecewise_window: float = 1.0        # PIECEWISE_WINDOW: a cell's half window in cell sizes
     piecewise_min_points: int = 6        # PIECEWISE_MIN_POINTS: fewer points, no cell fit
     piecewise_max_residual: float = 8.0  # PIECEWISE_MAX_RESIDUAL: px, larger residuals are dropped
+    # Opt-in (build-defined, K3c): the interpolation of every warp with 2 x 3 maps, "linear" (the
+    # reference's INTER_LINEAR) or "cubic" (kcmc_warp_affine_cubic_u16; parity with cv2
+    # unpinned).  Grayscale stacks and 2 x 3 maps only; the field warp stays bilinear.
+    warp_interpolation: str = "linear"
 
     @property
     def effective_frame_skip(self) -> int:
@@ -272,23 +276,48 @@ def postprocess_affines(params_host: np.ndarray, cfg: AlignConfig):
 
 
 def warp_frames(frames: torch.Tensor, maps: torch.Tensor, out: Optional[torch.Tensor] = None,
-                stream: Optional[int] = None) -> torch.Tensor:
-    """VA:150 on the device: warpAffine for [F, 2, 3] maps, warpPerspective for [F, 3, 3]."""
+                stream: Optional[int] = None, *, interpolation: str = "linear") -> torch.Tensor:
+    """VA:150 on the device: warpAffine for [F, 2, 3] maps, warpPerspective for [F, 3, 3].
+    interpolation="cubic": the bicubic warp (K3c), 2 x 3 maps and grayscale frames only."""
+    stages.check_interpolation(interpolation)
     if maps.shape[1:] == (3, 3):
+        if interpolation == "cubic":
+            raise NotImplementedError("interpolation='cubic' does not support [F, 3, 3] maps (warpPerspective "
+                                      "stays bilinear)")
         return stages.warp_perspective_u16(frames, maps, out=out, stream=stream)
-    return stages.warp_affine_u16(frames, maps, out=out, stream=stream)
+    return stages.warp_affine_u16(frames, maps, out=out, stream=stream, interpolation=interpolation)
 
 
-def warp_stage(frames: torch.Tensor, affines: np.ndarray, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def warp_stage(frames: torch.Tensor, affines: np.ndarray, out: Optional[torch.Tensor] = None, *,
+               interpolation: str = "linear") -> torch.Tensor:
+    stages.check_interpolation(interpolation)
     F = frames.shape[0]
     a = torch.from_numpy(np.ascontiguousarray(affines[:F], dtype=np.float64)).to(frames.device)
-    return warp_frames(frames, a, out=out)
+    return warp_frames(frames, a, out=out, interpolation=interpolation)
+
+
+def check_warp_interpolation(cfg: AlignConfig, frames_dim: Optional[int] = None) -> str:
+    """cfg.warp_interpolation, validated before any work: an unknown value is a ValueError and
+    the combinations the cubic warp does not cover refuse with a reason instead of resampling
+    bilinearly behind the caller's back.  frames_dim: the stack's rank (4: colour), when known."""
+    interp = stages.check_interpolation(cfg.warp_interpolation)
+    if interp == "cubic":
+        if cfg.ransac_model == "projective":
+            raise NotImplementedError("warp_interpolation='cubic' does not support ransac_model = 'projective' "
+                                      "(warpPerspective stays bilinear)")
+        if cfg.piecewise_grid is not None:
+            raise NotImplementedError("warp_interpolation='cubic' does not support piecewise_grid (the field warp "
+                                      "stays bilinear)")
+        if frames_dim is not None and frames_dim != 3:
+            raise NotImplementedError("warp_interpolation='cubic' supports grayscale stacks [F, H, W] only")
+    return interp
 
 
 def align_slab(inp: SlabInputs, cfg: AlignConfig, logger: Optional[logging.Logger] = None,
                out: Optional[torch.Tensor] = None, keep_intermediates: bool = False) -> SlabResult:
     """Run the whole hot path for one slab on the slab's device."""
     logger = logger or logging.getLogger("VideoAligner")
+    interp = check_warp_interpolation(cfg, inp.frames.dim())
     n_tpl = inp.des_tpl.shape[0]
     n_sample = inp.q_off.numel() - 1
     match = match_stage(inp, cfg)
@@ -303,7 +332,7 @@ def align_slab(inp: SlabInputs, cfg: AlignConfig, logger: Optional[logging.Logge
     if cfg.piecewise_grid is not None:
         aligned, extras = piecewise_stage(inp, cfg, match, cons, params, affines, out=out)
     else:
-        aligned = warp_stage(inp.frames, affines, out=out)
+        aligned = warp_stage(inp.frames, affines, out=out, interpolation=interp)
     return SlabResult(aligned, affines, eu, skipped, interpolated,
                       match if keep_intermediates else None, cons if keep_intermediates else None,
                       rr if keep_intermediates else None, counts, extras)
@@ -462,6 +491,7 @@ class OverlappedSlabs:
                  counts: Optional[List[int]] = None, group=None, match_beside: bool = False):
         self.match_beside = bool(match_beside)
         refuse_piecewise(cfg, "OverlappedSlabs")
+        self._interp = check_warp_interpolation(cfg)
         if counts is not None and len(counts) > 1 and cfg.frame_downsample_rate != 1:
             # the rank's first frame is counted in sample frames, the affines in full-rate
             # frames: the same restriction as distributed.align_sharded
@@ -717,7 +747,8 @@ class OverlappedSlabs:
         self._at_tail(mark, "w0")
         # one-call warp (plan + tiles) on the kernel stream: planning it on the analysis
         # stream behind RANSAC measured slower (profiles/r05_k_plan_beside_ab.txt)
-        p.aligned = warp_frames(p.inp.frames, p.rr.params, out=p.out, stream=self._hs)
+        p.aligned = warp_frames(p.inp.frames, p.rr.params, out=p.out, stream=self._hs,
+                                interpolation=self._interp)
         self._queued()
         self._at_tail(mark, "w1")
 
@@ -752,14 +783,14 @@ class OverlappedSlabs:
             redo[sk[(sk >= 0) & (sk < n)]] = True
             for a, b in _runs(redo):
                 (m,) = _h2d_async((local[a:b],), self.dev, self.copy)
-                warp_frames(p.inp.frames[a:b], m, out=p.aligned[a:b], stream=self._hs)
+                warp_frames(p.inp.frames[a:b], m, out=p.aligned[a:b], stream=self._hs, interpolation=self._interp)
                 self._queued()
             aligned = p.aligned
         else:
             (m,) = _h2d_async((local,), self.dev, self.copy)
             self._queued()
             self._at_tail(mark, "w0")
-            aligned = warp_frames(p.inp.frames, m, out=p.out, stream=self._hs)
+            aligned = warp_frames(p.inp.frames, m, out=p.out, stream=self._hs, interpolation=self._interp)
             self._queued()
             self._at_tail(mark, "w1")
         done = self._at_tail(mark)
@@ -811,6 +842,7 @@ def align_streamed(frames_host: torch.Tensor, inp: SlabInputs, cfg: AlignConfig,
     rate is bound by PCIe (both directions) rather than HBM.  Returns
     (out_host, SlabResult without the aligned tensor)."""
     refuse_piecewise(cfg, "align_streamed")
+    interp = check_warp_interpolation(cfg, frames_host.dim())
     dev = inp.des_tpl.device
     F = frames_host.shape[0]
     if out_host is None:
@@ -845,7 +877,7 @@ def align_streamed(frames_host: torch.Tensor, inp: SlabInputs, cfg: AlignConfig,
             s_cmp.wait_event(in_ready[b])
             if out_free[b] is not None:
                 s_cmp.wait_event(out_free[b])
-            warp_frames(bin_[b][:n], maps[f0:f0 + n], out=bout[b][:n])
+            warp_frames(bin_[b][:n], maps[f0:f0 + n], out=bout[b][:n], interpolation=interp)
             ev = torch.cuda.Event()
             ev.record(s_cmp)
             in_free[b] = ev

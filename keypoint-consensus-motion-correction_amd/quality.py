@@ -98,7 +98,7 @@ def _invert_affines(affines: np.ndarray) -> np.ndarray:
     return M
 
 
-def valid_region(affines: np.ndarray, H: int, W: int) -> Region:
+def valid_region(affines: np.ndarray, H: int, W: int, taps: int = 2) -> Region:
     """(y0, y1, x0, x1): the rectangle [m, H - m) x [m, W - m) whose pixels no frame's warp
     fills from outside the source image.  m = ceil(d) + 1, d the largest displacement
     |M_f^-1(c) - c| (max norm) over the frames and the four corners c of the pixel rectangle:
@@ -111,7 +111,15 @@ def valid_region(affines: np.ndarray, H: int, W: int) -> Region:
     integer counts as that integer.  That is far above float64's rounding of these few
     products and sums and far below what the margin needs: x in [m, W - 1 - m] reads source
     column x + disp, rounded to the fixed point by less than 1/16 px, and both taps are inside
-    while that lies in [0, W - 1), i.e. while m > d + 1/16; m >= d - tol + 1 keeps that."""
+    while that lies in [0, W - 1), i.e. while m > d + 1/16; m >= d - tol + 1 keeps that.
+
+    taps = 4 (the bicubic warp, K3c): m = ceil(d - tol) + 2.  The footprint reaches one pixel
+    further on each side: a pixel whose fixed-point source column is c reads columns
+    floor(c) - 1 .. floor(c) + 2, all inside the image (an interior pixel of the definition)
+    while c lies in [1, W - 2).  For x in [m, W - 1 - m], c is within d + 1/16 of x, so that
+    holds while m > d + 1 + 1/16, and m >= d - tol + 2 keeps it; the same in y."""
+    if taps not in (2, 4):
+        raise ValueError(f"valid_region: taps must be 2 (bilinear) or 4 (bicubic), got {taps!r}")
     a = np.asarray(affines, dtype=np.float64)
     if a.ndim == 3 and a.shape[1:] == (3, 3):
         raise NotImplementedError("valid_region: homographies are not supported (a projective displacement field "
@@ -129,7 +137,7 @@ def valid_region(affines: np.ndarray, H: int, W: int) -> Region:
         d = float(np.abs(mapped - corners[None]).max())
         if not math.isfinite(d):
             raise ValueError("valid_region: non-finite displacement")
-    m = math.ceil(d - (H + W) * 2.0 ** -40) + 1
+    m = math.ceil(d - (H + W) * 2.0 ** -40) + taps // 2
     if 2 * m >= min(H, W):
         raise ValueError("no common valid region")
     return m, H - m, m, W - m

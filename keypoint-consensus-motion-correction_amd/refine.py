@@ -43,7 +43,7 @@ from . import fallback as _fb
 from . import quality as _q
 from ._intensity import Frames, Region
 from .pipeline import _runs, summary_transforms
-from .stages import warp_affine_u16
+from .stages import check_interpolation, warp_affine_u16
 
 MOTIONS = ("rigid", "translation")
 _CHUNK = 256  # frames warped and measured at a time (the candidates' scratch)
@@ -266,12 +266,15 @@ class RefineResult:
 
 def refine_frames(res, sources: Sequence[torch.Tensor], n_images: int, rate: int, model: str, iters: int = 2,
                   motion: str = "rigid", max_step: float = 1.0,
-                  logger: Optional[logging.Logger] = None) -> RefineResult:
+                  logger: Optional[logging.Logger] = None, interpolation: str = "linear") -> RefineResult:
     """The pass over one result of the hot path (``res``: a SlabResult or SplitResult whose
     aligned frames are still on their devices; ``sources``: each slab's source frames).
     Changes ``res`` in place: the changed frames' rows of the aligned stack, of ``affines``
-    and of the transform summary.  ``res.skipped`` / ``res.interpolated`` stay what they are."""
+    and of the transform summary.  ``res.skipped`` / ``res.interpolated`` stay what they are.
+    ``interpolation``: the warp's ("linear" or "cubic"); the candidates are warped with it and
+    the valid region is the one of its footprint."""
     check_options(iters, motion, max_step)
+    taps = 4 if check_interpolation(interpolation) == "cubic" else 2
     iters = int(iters)
     parts = _in.pass_parts("intensity refinement", res)
     H, W = parts[0].shape[1:]
@@ -283,7 +286,7 @@ def refine_frames(res, sources: Sequence[torch.Tensor], n_images: int, rate: int
     for it in range(iters):
         try:
             ref = _q.mean_image(parts, sel)
-            rect = _q.valid_region(np.asarray(res.affines)[:n], H, W)
+            rect = _q.valid_region(np.asarray(res.affines)[:n], H, W, taps=taps)
             rows = band_rows(H, W, rect)
         except ValueError as e:
             info(f"intensity refinement, iteration {it + 1}: nothing refined ({e})")
@@ -300,7 +303,7 @@ def refine_frames(res, sources: Sequence[torch.Tensor], n_images: int, rate: int
         # the candidates, warped from their source frames
         for src, dst, f0, a, b in _in.rewarp_runs(sources, parts, new_maps, _CHUNK):
             maps = torch.from_numpy(np.stack([new_maps[f0 + j] for j in range(a, b)])).to(dst.device)
-            cand = warp_affine_u16(src[a:b], maps)
+            cand = warp_affine_u16(src[a:b], maps, interpolation=interpolation)
             r_new = _q.frame_correlations(cand, ref, rect)
             rose = r_new > st[f0 + a:f0 + b, 4]  # kept only there (NaN: not kept)
             for ra, rb in _runs(rose):

@@ -600,12 +600,28 @@ def ransac_lists(model: str, src: torch.Tensor, dst: torch.Tensor, pt_off: torch
 
 
 # ----------------------------------------------------------------------- K3
+WARP_INTERPOLATIONS = ("linear", "cubic")
+
+
+def check_interpolation(interpolation) -> str:
+    """The warp's interpolation switch: "linear" (the reference's INTER_LINEAR) or "cubic"."""
+    if interpolation not in WARP_INTERPOLATIONS:
+        raise ValueError(f"interpolation must be one of {WARP_INTERPOLATIONS}, got {interpolation!r}")
+    return interpolation
+
+
 def warp_affine_u16(frames: torch.Tensor, affines: torch.Tensor, out: Optional[torch.Tensor] = None,
-                    inverse_map: bool = False, stream: Optional[int] = None) -> torch.Tensor:
+                    inverse_map: bool = False, stream: Optional[int] = None,
+                    interpolation: str = "linear") -> torch.Tensor:
     """cv2.warpAffine(frame, M, (W, H), INTER_LINEAR) for every frame (VA:458).
 
     frames [F, H, W] or [F, H, W, C] uint16 on the device; affines [F, 2, 3] f64.
+    interpolation="cubic": the bicubic warp (K3c, build-defined: include/kcmc.h; parity with
+    cv2 unpinned), grayscale [F, H, W] only.
     """
+    check_interpolation(interpolation)
+    if interpolation == "cubic" and frames.dim() == 4:
+        raise NotImplementedError("interpolation='cubic' is grayscale only: frames must be [F, H, W]")
     dev = _device_of(frames)
     if frames.dtype != torch.uint16:
         raise TypeError(f"frames: expected torch.uint16, got {frames.dtype}")
@@ -624,8 +640,9 @@ def warp_affine_u16(frames: torch.Tensor, affines: torch.Tensor, out: Optional[t
         if out.shape != frames.shape:
             raise ValueError("out must have the shape of frames")
     L = _lib.load()
-    _lib.check(L.kcmc_warp_affine_u16(_ctx(dev).handle, _ptr(frames), _ptr(out), _ptr(affines), F, H, W, C,
-                                      int(bool(inverse_map)), _stream(dev, stream)))
+    entry = L.kcmc_warp_affine_cubic_u16 if interpolation == "cubic" else L.kcmc_warp_affine_u16
+    _lib.check(entry(_ctx(dev).handle, _ptr(frames), _ptr(out), _ptr(affines), F, H, W, C,
+                     int(bool(inverse_map)), _stream(dev, stream)))
     return out
 
 

@@ -211,6 +211,16 @@ class VideoAligner:
     # refine_field_idxs.  Not with QUALITY_METRICS / TEMPLATE_REFINE_ITERS.
     REFINE_GRID: Optional[Tuple[int, int]] = None
     REFINE_GRID_ITERS = 1
+    # New (opt-in, csrc/warp_cubic.hip; build-defined, the reference always resamples with
+    # INTER_LINEAR): the interpolation of every warp of the frames.  "linear": the reference's.
+    # "cubic": OpenCV's classic INTER_CUBIC restated (cubic convolution, A = -3/4, 4 x 4 taps;
+    # include/kcmc.h; parity with cv2 unpinned) -- aligned_imgs, the fallback's and the
+    # refinement's warps and _apply_affine resample bicubically and valid_region keeps the wider
+    # footprint's margin; transforms, affines, skipped_idxs and interpolated_idxs are what they
+    # are with "linear" (the intensity passes read the resampled frames, so their corrections may
+    # differ).  Grayscale stacks, 2 x 3 models, not with PIECEWISE_GRID / REFINE_GRID (the field
+    # warp stays bilinear).
+    WARP_INTERPOLATION = "linear"
 
     def __init__(self, logger: LoggerAdapter = None):
         self.logger = logger
@@ -269,7 +279,32 @@ class VideoAligner:
             match_norm=cls.MATCH_NORM,
             piecewise_grid=None if cls.PIECEWISE_GRID is None else _pw.check_grid(cls.PIECEWISE_GRID),
             piecewise_window=float(cls.PIECEWISE_WINDOW), piecewise_min_points=int(cls.PIECEWISE_MIN_POINTS),
-            piecewise_max_residual=float(cls.PIECEWISE_MAX_RESIDUAL))
+            piecewise_max_residual=float(cls.PIECEWISE_MAX_RESIDUAL),
+            warp_interpolation=stages.check_interpolation(cls.WARP_INTERPOLATION))
+
+    # ------------------------------------------------------------- the warp's interpolation
+    def _interpolation_on(self, images=None) -> str:
+        """WARP_INTERPOLATION, after the checks that must fail before any work (``images``: only
+        its number of dimensions is read, when it has one)."""
+        try:
+            interp = stages.check_interpolation(self.WARP_INTERPOLATION)
+        except ValueError:
+            raise ValueError("WARP_INTERPOLATION must be 'linear' or 'cubic', got "
+                             f"{self.WARP_INTERPOLATION!r}") from None
+        if interp == "linear":
+            return interp
+        if self.RANSAC_MODEL == "projective":
+            raise NotImplementedError("WARP_INTERPOLATION = 'cubic' does not support RANSAC_MODEL = 'projective' "
+                                      "(warpPerspective stays bilinear)")
+        if getattr(images, "ndim", 3) != 3:
+            raise NotImplementedError("WARP_INTERPOLATION = 'cubic' supports grayscale stacks [F, H, W] only")
+        if self.PIECEWISE_GRID is not None:
+            raise NotImplementedError("WARP_INTERPOLATION = 'cubic' does not run together with PIECEWISE_GRID (the "
+                                      "field warp stays bilinear)")
+        if self.REFINE_GRID is not None:
+            raise NotImplementedError("WARP_INTERPOLATION = 'cubic' does not run together with REFINE_GRID (the "
+                                      "field warp stays bilinear)")
+        return interp
 
     # ------------------------------------------------------------- piecewise-rigid correction
     def _reset_piecewise(self) -> None:
@@ -343,7 +378,8 @@ class VideoAligner:
             res = hot()
             fb = _fb.correct_skipped(res, [inp.frames for inp in slabs], n_images, rate, self.RANSAC_MODEL,
                                      int(self.FALLBACK_RADIUS), float(self.FALLBACK_MIN_CORRELATION),
-                                     bool(self.FALLBACK_SUBPIXEL), logger=self.logger)
+                                     bool(self.FALLBACK_SUBPIXEL), logger=self.logger,
+                                     interpolation=self._interpolation_on())
             self.fallback_shifts, self.fallback_correlations = fb.shifts, fb.correlations
             self.fallback_idxs = fb.idxs
             self.affines = res.affines
@@ -399,7 +435,7 @@ class VideoAligner:
             res = hot()
             rf = _rf.refine_frames(res, [inp.frames for inp in slabs], n_images, rate, self.RANSAC_MODEL,
                                    int(self.REFINE_ITERS), self.REFINE_MOTION, float(self.REFINE_MAX_STEP),
-                                   logger=self.logger)
+                                   logger=self.logger, interpolation=self._interpolation_on())
             self.refine_steps, self.refine_correlations, self.refine_idxs = rf.steps, rf.correlations, rf.idxs
             self.affines = res.affines
             if self._refine_grid_on():
@@ -444,7 +480,8 @@ class VideoAligner:
         sel = _in.sample_mask(n_images, rate, res.skipped)
         mean0 = _q.mean_image(parts, sel)
         self.affines = res.affines
-        region = _q.valid_region(np.asarray(res.affines)[:n_images], H, W)
+        region = _q.valid_region(np.asarray(res.affines)[:n_images], H, W,
+                                 taps=4 if self._interpolation_on() == "cubic" else 2)
         corr = _q.frame_correlations(parts, mean0, region)
         self.mean_image = mean0.cpu().numpy()
         self.valid_region = region
@@ -508,6 +545,7 @@ class VideoAligner:
         skipped_idxs); with RANSAC_MODEL = "similarity" the transforms are [n, 4] = (tx, ty,
         rotation, scale).  A device tensor input yields a device tensor output.
         """
+        self._interpolation_on(images)
         self._reset_quality()
         self._quality_on()
         self._reset_piecewise()
@@ -688,6 +726,8 @@ class VideoAligner:
         hot = self._with_refine(hot, slabs, n_images, rate)
         res = self._run_passes(hot, slabs, n_images, rate, detect_template)
         self.interpolated_idxs = res.interpolated
+        if self._interpolation_on() == "cubic":  # the maps the frames were resampled with
+            self.affines = res.affines
         self.logger.info(f"aligned frames in: {round(time.time() - t_start)} s")
         aligned = _md.gather_aligned(res, out_device)
         if patch is not None:
@@ -717,6 +757,7 @@ class VideoAligner:
         """The hot path with precomputed keypoints: per SAMPLE frame
         (images[::max(1, frame_rate // FRAME_SAMPLE_RATE)]) keypoint coordinates [n, 2]
         and uint8 descriptors [n, D]; template keypoints/descriptors likewise."""
+        self._interpolation_on(images)
         self._reset_quality()
         self._quality_on(refine_supported=False)
         self._reset_piecewise()
@@ -765,6 +806,8 @@ class VideoAligner:
         hot = self._with_refine(hot, [inp], n_images, rate)
         res = self._run_passes(hot, [inp], n_images, rate, detect_template)
         self.interpolated_idxs = res.interpolated
+        if self._interpolation_on() == "cubic":  # the maps the frames were resampled with
+            self.affines = res.affines
         self.logger.info(f"aligned frames in: {round(time.time() - t_start)} s")
         self._take_piecewise(res)
         aligned = res.aligned
@@ -887,11 +930,13 @@ class VideoAligner:
 
     @classmethod
     def _apply_affine(cls, image: np.ndarray, affine: np.ndarray) -> np.ndarray:
-        """VA:455-458: cv2.warpAffine(image, affine, (W, H), INTER_LINEAR) on the GPU."""
+        """VA:455-458: cv2.warpAffine(image, affine, (W, H), INTER_LINEAR) on the GPU (the
+        bicubic warp with WARP_INTERPOLATION = "cubic")."""
         dev = cls._device()
         img = torch.from_numpy(np.ascontiguousarray(image, np.uint16)[None]).to(dev)
         a = torch.from_numpy(np.ascontiguousarray(affine, np.float64).reshape(1, 2, 3)).to(dev)
-        return stages.warp_affine_u16(img, a).cpu().numpy()[0]
+        return stages.warp_affine_u16(img, a, interpolation=stages.check_interpolation(cls.WARP_INTERPOLATION)
+                                      ).cpu().numpy()[0]
 
     def _parallelize(self, func: Callable, *sequences: Sequence, **kwargs) -> List:
         """VA:460-465: func over the equal-length sequences, results in order, in a joblib
