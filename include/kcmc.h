@@ -36,6 +36,9 @@
  *   kcmc_tile_gradient_sums_u16 <- nothing in the reference (an extension): the same
  *                             right-hand side on every patch of a tiling from one read of
  *                             the stack, for the non-rigid intensity refinement.
+ *   kcmc_bidi_phase_sums_u16 / kcmc_shift_rows_u16 <- nothing in the reference (an extension):
+ *                             the offset of the odd rows of a bidirectionally scanned stack
+ *                             against its even rows, measured and undone before registration.
  *
  * Conventions
  *   - Plain pointers and sizes only.  Pointers named *_dev are device (HBM) pointers
@@ -624,6 +627,53 @@ int kcmc_tile_gradient_sums_u16(kcmc_ctx* ctx, const uint16_t* frames_dev, int n
                                 const int32_t* frame_idx_dev, int n_sel, const uint16_t* ref_dev,
                                 const int32_t* row_edges_host, int ty, const int32_t* col_edges_host, int tx,
                                 long long* out_dev, kcmc_stream_t stream);
+
+/* ----------------------------- b1: bidirectional-scan phase correction (row offset)
+ * Build-defined: the reference has no such mode.  A microscope that scans bidirectionally
+ * acquires the odd image rows on the return sweep; an error in its line clock displaces every
+ * odd row horizontally against the even rows by a constant.  These two entry points measure
+ * that offset in whole pixels and undo it (host part: kcmc_amd.bidi; numpy restatement:
+ * tests/test_bidi_host.py).
+ *
+ * out_dev [n_sel, 2R + 1, 5] u64: for the selected frame F = frames_dev[frame_idx_dev[s]]
+ * (frames_dev [n_frames, H, W] u16) and every d in [-R, R], entry [s][d + R] = (sum a, sum b,
+ * sum a^2, sum b^2, sum a*b) -- the layout of kcmc_frame_stats_u16 -- over the samples
+ *   one vertically adjacent row pair (y, y + 1), 0 <= y < H - 1, at one column x in [R, W - R):
+ *   a = F[the pair's odd row][x + d],  b = F[the pair's even row][x].
+ * There are n = (H - 1) (W - 2R) samples for every d; an interior row is in two pairs and counts
+ * twice.  A high correlation at d says odd(x + d) ~ even(x): the odd rows are corrected by
+ * kcmc_shift_rows_u16(..., parity = 1, d).
+ *
+ * frame_idx_dev [n_sel] i32; NULL = frames 0 .. n_sel - 1.  An index outside [0, n_frames)
+ * gives an all-zero row and is never read through; repeated and unordered indices are fine.
+ *
+ * Contract (KCMC_EINVAL before any device work otherwise, as for a NULL ctx or pointer):
+ * 0 <= R <= 16, H >= 2, W >= 2R + 1, H * W < 2^31 (every sum stays below 2^63), out_dev 8-byte
+ * aligned.  n_sel == 0 is KCMC_OK.  Any alignment of frames_dev and any W: the 16-byte path needs
+ * W % 8 == 0 and a 16-byte aligned frames_dev, everything else is read element by element.  No
+ * load leaves the image.
+ *
+ * Exact: every sum is a 64-bit integer (no floating point), added into the zeroed output with
+ * 64-bit integer atomics, so nothing depends on the order in which workgroups finish.
+ * Asynchronous on `stream`, no allocation; zeroes its own output first. */
+int kcmc_bidi_phase_sums_u16(kcmc_ctx* ctx, const uint16_t* frames_dev, int n_frames, int H, int W,
+                             const int32_t* frame_idx_dev, int n_sel, int R, uint64_t* out_dev,
+                             kcmc_stream_t stream);
+
+/* dst_dev[f][y][x] = src_dev[f][y][clamp(x + d, 0, W - 1)] for the rows with (y & 1) == parity and
+ * src_dev[f][y][x] for the others; src_dev / dst_dev [n_frames, H, W] u16.  The edge pixel is
+ * replicated, not zero-filled (a comb of zeros at the border would hand the detector corners).
+ * parity is 0 or 1; |d| <= 16, also when that exceeds W (the clamp covers it: the shifted rows are
+ * then filled with their edge pixel); H, W < 32768.
+ * src_dev == dst_dev is allowed -- in place, and then only the rows of the parity are touched (with
+ * d == 0 nothing is launched); any other overlap of the two stacks is KCMC_EINVAL.  Out of place
+ * every row is written (d == 0: a copy) and src_dev is only read.  n_frames == 0 is KCMC_OK; a NULL
+ * ctx or pointer and arguments outside the limits are KCMC_EINVAL before any device work.  Any
+ * alignment and any W: 16-byte loads and stores need W % 8 == 0 and 16-byte aligned stacks (and a
+ * row of at most 32728 pixels), everything else moves element by element.  A workgroup reads a row
+ * completely before any of it is written.  Asynchronous on `stream`, no allocation. */
+int kcmc_shift_rows_u16(kcmc_ctx* ctx, const uint16_t* src_dev, uint16_t* dst_dev, int n_frames, int H, int W,
+                        int parity, int d, kcmc_stream_t stream);
 
 #ifdef __cplusplus
 }

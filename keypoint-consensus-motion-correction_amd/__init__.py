@@ -9,10 +9,10 @@ include/kcmc.h); the host keeps the reference's Python API.
 Import as ``import kcmc_amd`` (the repository-root shim ``kcmc_amd.py`` maps that
 name onto this directory).
 """
-from . import fallback, piecewise, quality, refine, refine_field
+from . import bidi, fallback, piecewise, quality, refine, refine_field
 from .affines import AlignmentError
 from .video_aligner import LoResVideoAligner, VideoAligner
 
-__all__ = ["VideoAligner", "LoResVideoAligner", "AlignmentError", "fallback", "piecewise", "quality", "refine",
+__all__ = ["VideoAligner", "LoResVideoAligner", "AlignmentError", "bidi", "fallback", "piecewise", "quality", "refine",
            "refine_field"]
 __version__ = "0.1.0"

@@ -64,6 +64,8 @@ EXPORTED_SYMBOLS = (
     "kcmc_shift_search_u16",
     "kcmc_gradient_sums_u16",
     "kcmc_tile_gradient_sums_u16",
+    "kcmc_bidi_phase_sums_u16",
+    "kcmc_shift_rows_u16",
 )
 
 KCMC_MODEL_EUCLIDEAN = 0
@@ -138,6 +140,8 @@ _SIGNATURES = {
     "kcmc_shift_search_u16": ([P, P, I, I, I, P, I, P, I, I, I, I, I, P, P], I),
     "kcmc_gradient_sums_u16": ([P, P, I, I, I, P, I, P, I, I, I, I, I, P, P], I),
     "kcmc_tile_gradient_sums_u16": ([P, P, I, I, I, P, I, P, P, I, P, I, P, P], I),
+    "kcmc_bidi_phase_sums_u16": ([P, P, I, I, I, P, I, I, P, P], I),
+    "kcmc_shift_rows_u16": ([P, P, P, I, I, I, I, I, P], I),
 }
 
 

@@ -31,6 +31,7 @@ import torch
 
 from . import affines as _aff
 from . import _intensity as _in
+from . import bidi as _bd
 from . import fallback as _fb
 from . import multidevice as _md
 from . import piecewise as _pw
@@ -221,6 +222,25 @@ class VideoAligner:
     # differ).  Grayscale stacks, 2 x 3 models, not with PIECEWISE_GRID / REFINE_GRID (the field
     # warp stays bilinear).
     WARP_INTERPOLATION = "linear"
+    # New (opt-in, kcmc_amd.bidi; build-defined, the reference has no such mode): the phase
+    # correction of bidirectionally scanned stacks, whose odd rows are displaced horizontally
+    # against the even rows by a constant.  "none": off.  "auto": the offset is measured on
+    # bidi.sample_indices(n, BIDI_PHASE_FRAMES) of the raw frames -- Pearson's r of the odd rows
+    # read at x + d with their even neighbours at x for every d within BIDI_PHASE_RADIUS, from
+    # exact integer sums pooled over the frames (csrc/bidi_phase.hip) -- and the peak is taken
+    # unless it sits on the window's border or gains no more than BIDI_PHASE_MIN_GAIN over
+    # d = 0.  An int in [-16, 16]: applied as given.  A non-zero offset d replaces every odd row
+    # by row[clamp(x + d)] (whole pixels, the edge pixel replicated; up to half a pixel
+    # remains) once the frames are on their device(s) and before anything else: the corrected
+    # stack is the source of the normalisation, the detection, the template frame, every warp
+    # and every later pass, exactly as if the caller had passed it.  The aligner's own upload
+    # is corrected in place, a caller's device tensor into a new one (memory the caller can see
+    # is never written).  Results: bidi_offset, bidi_correlations, bidi_frames, bidi_accepted.
+    # Grayscale stacks.
+    BIDI_PHASE: Union[str, int] = "none"
+    BIDI_PHASE_RADIUS = 8           # 1..16 px
+    BIDI_PHASE_FRAMES = 64          # >= 1
+    BIDI_PHASE_MIN_GAIN = 0.0
 
     def __init__(self, logger: LoggerAdapter = None):
         self.logger = logger
@@ -236,6 +256,7 @@ class VideoAligner:
         self._reset_piecewise()
         self._reset_fallback()
         self._reset_refine()
+        self._reset_bidi()
 
     # ------------------------------------------------------------------ helpers
     @classmethod
@@ -305,6 +326,78 @@ class VideoAligner:
             raise NotImplementedError("WARP_INTERPOLATION = 'cubic' does not run together with REFINE_GRID (the "
                                       "field warp stays bilinear)")
         return interp
+
+    # ------------------------------------------------- bidirectional-scan phase correction
+    def _reset_bidi(self) -> None:
+        self.bidi_offset = None
+        self.bidi_correlations = None
+        self.bidi_frames = None
+        self.bidi_accepted = None
+
+    def _bidi_on(self, images=None):
+        """BIDI_PHASE -- None for "none", else "auto" or the int -- after the checks that must fail
+        before any work (``images``: only its number of dimensions is read, when it has one)."""
+        mode = self.BIDI_PHASE
+        if isinstance(mode, str):
+            if mode == "none":
+                return None
+            if mode != "auto":
+                raise ValueError(f"BIDI_PHASE must be 'none', 'auto' or an integer in [-16, 16], got {mode!r}")
+        else:
+            try:
+                mode = _bd.check_shift(mode)
+            except ValueError:
+                raise ValueError("BIDI_PHASE must be 'none', 'auto' or an integer in [-16, 16], got "
+                                 f"{self.BIDI_PHASE!r}") from None
+        radius, k, gain = self.BIDI_PHASE_RADIUS, self.BIDI_PHASE_FRAMES, self.BIDI_PHASE_MIN_GAIN
+        if not (_bd._is_int(radius) and 1 <= int(radius) <= _bd.MAX_RADIUS):
+            raise ValueError(f"BIDI_PHASE_RADIUS must be an integer in [1, {_bd.MAX_RADIUS}], got {radius!r}")
+        if not (_bd._is_int(k) and int(k) >= 1):
+            raise ValueError(f"BIDI_PHASE_FRAMES must be an integer >= 1, got {k!r}")
+        if isinstance(gain, bool) or not isinstance(gain, (int, float, np.integer, np.floating)) or gain != gain:
+            raise ValueError(f"BIDI_PHASE_MIN_GAIN must be a number, got {gain!r}")
+        if getattr(images, "ndim", 3) != 3:
+            raise NotImplementedError("BIDI_PHASE supports grayscale stacks [F, H, W] only")
+        return mode
+
+    def _bidi_correct(self, parts: List[torch.Tensor], own: bool) -> List[torch.Tensor]:
+        """The slabs of the stack with the phase correction applied (``parts`` themselves with the
+        switch off or an offset of 0).  ``own``: the slabs are the aligner's own upload and are
+        corrected in place; otherwise into new tensors."""
+        mode = self._bidi_on()
+        if mode is None:
+            return parts
+        if not own:
+            parts = [p.contiguous() for p in parts]
+        if mode == "auto":
+            R = int(self.BIDI_PHASE_RADIUS)
+            H, W = parts[0].shape[1:]
+            idx = _bd.sample_indices(sum(p.shape[0] for p in parts), int(self.BIDI_PHASE_FRAMES))
+            off, r, ok = _bd.estimate_offset(_bd.phase_sums(parts, idx, R), _bd.sample_count(H, W, R),
+                                             float(self.BIDI_PHASE_MIN_GAIN))
+            self.bidi_correlations, self.bidi_frames, self.bidi_accepted = r, idx, ok
+            self.logger.info(f"bidirectional phase: offset {off} px from {len(idx)} frames"
+                             + ("" if ok else " (no acceptable peak)"))
+        else:
+            off = int(mode)
+            self.bidi_correlations, self.bidi_frames, self.bidi_accepted = None, [], True
+        self.bidi_offset = off
+        if off != 0:
+            parts = _bd.shift_rows(parts, off, 1, out=parts if own else None)
+        return parts
+
+    def _bidi_source(self, parts, own: bool, template, template_idx: Optional[int]):
+        """(_bidi_correct(parts, own), the template): the template frame is taken again from the
+        corrected stack when it came from the stack (``template_idx``; None: a masked_template,
+        which is used as given)."""
+        parts = self._bidi_correct(parts, own)
+        if self.bidi_offset and template_idx is not None:
+            f0 = 0
+            for p in parts:
+                if f0 <= template_idx < f0 + p.shape[0]:
+                    template = _as_numpy(p[template_idx - f0])
+                f0 += p.shape[0]
+        return parts, template
 
     # ------------------------------------------------------------- piecewise-rigid correction
     def _reset_piecewise(self) -> None:
@@ -544,8 +637,13 @@ class VideoAligner:
         Returns (aligned_imgs, euclidean_transforms [n, 3] = (tx, ty, rotation),
         skipped_idxs); with RANSAC_MODEL = "similarity" the transforms are [n, 4] = (tx, ty,
         rotation, scale).  A device tensor input yields a device tensor output.
+
+        With BIDI_PHASE on, the template frame is taken from the corrected stack; a
+        ``masked_template`` is used as given (the caller corrects it, bidi.shift_rows).
         """
         self._interpolation_on(images)
+        self._reset_bidi()
+        self._bidi_on(images)
         self._reset_quality()
         self._quality_on()
         self._reset_piecewise()
@@ -560,6 +658,7 @@ class VideoAligner:
             raise ValueError("`template_frame_loc` must be between 0 and 1")
         on_device = isinstance(images, torch.Tensor)
         images_np = None if on_device else np.asarray(images)
+        template_idx = None
         if masked_template is not None:
             template = _as_numpy(masked_template)
         else:
@@ -572,7 +671,7 @@ class VideoAligner:
         ranges = _md.split_frames(len(images), frame_downsample_rate, len(devices))
         if len(ranges) > 1:
             return self._align_images_split(images, template, n_kp_global, detector_algorithm, frame_downsample_rate,
-                                            patch, devices[:len(ranges)], ranges)
+                                            patch, devices[:len(ranges)], ranges, template_idx)
 
         self.logger.info("normalizing frames...")
         t_start = time.time()
@@ -582,6 +681,7 @@ class VideoAligner:
         assert (images.dtype == torch.uint16) if on_device else (images_np.dtype == np.uint16)  # VA:104
         dev = self._device()
         frames = images if on_device else torch.from_numpy(np.ascontiguousarray(images_np)).to(dev)
+        (frames,), template = self._bidi_source([frames], not on_device, template, template_idx)
         brightest_px = self._get_brightest_px(frames)
         u8_dev = self._max_scale_images(frames, None, brightest_px, np.uint8)[0]
         _, template_i8 = self._max_scale_images(None, template, brightest_px, np.uint8)
@@ -647,7 +747,8 @@ class VideoAligner:
 
         return detect_template
 
-    def _align_images_split(self, images, template, n_kp_global, detector_algorithm, rate, patch, devices, ranges):
+    def _align_images_split(self, images, template, n_kp_global, detector_algorithm, rate, patch, devices, ranges,
+                            template_idx=None):
         """align_images with the stack split over several devices (kcmc_amd.multidevice):
         each slab's frames uploaded to its device, the 99.99th percentile of the whole stack
         from the summed per-device histograms, max-scaling and (GPU detector) detection per
@@ -657,6 +758,7 @@ class VideoAligner:
         t_start = time.time()
         assert (images.dtype == torch.uint16) if on_device else (np.asarray(images).dtype == np.uint16)  # VA:104
         parts = _md.split_to_devices(images if on_device else np.asarray(images), ranges, devices)
+        parts, template = self._bidi_source(parts, not on_device, template, template_idx)
         brightest_px = stages.brightest_px(parts, self.IMAGE_NORM_MAX_PERCENTILE)
         u8_parts = []
         for p in parts:  # each slab's work under its own device (launches, workspaces, allocations)
@@ -758,6 +860,8 @@ class VideoAligner:
         (images[::max(1, frame_rate // FRAME_SAMPLE_RATE)]) keypoint coordinates [n, 2]
         and uint8 descriptors [n, D]; template keypoints/descriptors likewise."""
         self._interpolation_on(images)
+        self._reset_bidi()
+        self._bidi_on(images)
         self._reset_quality()
         self._quality_on(refine_supported=False)
         self._reset_piecewise()
@@ -771,21 +875,27 @@ class VideoAligner:
         self._des_template = np.asarray(des_template, dtype=np.uint8)
         rate = max(1, frame_rate // self.FRAME_SAMPLE_RATE)
         return self._align_detected(images, self._kp_template, self._des_template, list(kp_query), list(des_query),
-                                    n_kp_global, rate, patch)
+                                    n_kp_global, rate, patch, bidi=True)
 
     def _align_detected(self, images, kp_template, des_template, kp_list, des_list, n_kp_global, rate, patch,
-                        detect_template=None):
+                        detect_template=None, bidi: bool = False):
+        """``bidi``: the frames are the caller's and take the phase correction here (align_images
+        has applied it before it detects)."""
         to_host = not isinstance(images, torch.Tensor)
         kp_flat, des_flat, q_off = self._csr(kp_list, des_list, des_template.shape[1])
         devices = self._devices()
         ranges = _md.split_frames(len(images), rate, len(devices))
         if len(ranges) > 1:  # every device its slab of frames (kcmc_amd.multidevice)
             parts = _md.split_to_devices(images if not to_host else np.asarray(images), ranges, devices)
+            if bidi:
+                parts = self._bidi_correct(parts, to_host)
             slabs = _md.make_slabs(parts, ranges, des_template, kp_template, kp_flat, des_flat, q_off)
             return self._finish_split(slabs, ranges, self._config(n_kp_global, rate), patch,
                                       None if to_host else images.device, detect_template)
         dev = torch.device("cuda", devices[0])
         frames = torch.from_numpy(np.ascontiguousarray(images)).to(dev) if to_host else images.contiguous()
+        if bidi:
+            frames = self._bidi_correct([frames], to_host)[0]
         inp = _pl.SlabInputs(
             frames=frames,
             des_tpl=torch.from_numpy(np.ascontiguousarray(des_template, np.uint8)).to(dev),
