@@ -93,18 +93,23 @@ class SlabResult:
     extras: dict = field(default_factory=dict)
 
 
+def frame_counts_text(i: int, c) -> str:
+    """The log text of VA:215-221 for frame ``i`` from its four match counts."""
+    return (
+        f"frame {i}:\n"
+        f"\t{int(c[0])} unfiltered features identified\n"
+        f"\t{int(c[1])} matches identified between frame and template\n"
+        f"\t{int(c[2])} matches after feature-space ratio filter\n"
+        f"\t{int(c[3])} matches after distance-based outlier rejection"
+    )
+
+
 def log_frame_counts(logger: logging.Logger, counts: np.ndarray, first_index: int = 0) -> None:
     """The per-frame debug lines of VA:215-221 / VA:125-126."""
     if not logger.isEnabledFor(logging.DEBUG):
         return
     for k, c in enumerate(counts):
-        logger.debug(
-            f"frame {first_index + k}:\n"
-            f"\t{int(c[0])} unfiltered features identified\n"
-            f"\t{int(c[1])} matches identified between frame and template\n"
-            f"\t{int(c[2])} matches after feature-space ratio filter\n"
-            f"\t{int(c[3])} matches after distance-based outlier rejection"
-        )
+        logger.debug(frame_counts_text(first_index + k, c))
 
 
 def _nomark(name, ev=None):

@@ -432,8 +432,6 @@ class VideoAligner:
         self.patch_residuals = ex.get("patch_residuals")
         self.patch_points = ex.get("patch_points")
         self.patch_fitted = ex.get("patch_fitted")
-        if self.patch_residuals is not None:  # the maps the field was added to
-            self.affines = res.affines
 
     def _check_intensity_pass(self, switch: str, why: str, images) -> None:
         """What the fallback and the refinement both refuse (``why``: what rules a homography out)."""
@@ -475,7 +473,6 @@ class VideoAligner:
                                      interpolation=self._interpolation_on())
             self.fallback_shifts, self.fallback_correlations = fb.shifts, fb.correlations
             self.fallback_idxs = fb.idxs
-            self.affines = res.affines
             return res
 
         return corrected
@@ -530,7 +527,6 @@ class VideoAligner:
                                    int(self.REFINE_ITERS), self.REFINE_MOTION, float(self.REFINE_MAX_STEP),
                                    logger=self.logger, interpolation=self._interpolation_on())
             self.refine_steps, self.refine_correlations, self.refine_idxs = rf.steps, rf.correlations, rf.idxs
-            self.affines = res.affines
             if self._refine_grid_on():
                 ff = _rff.refine_field_frames(res, [inp.frames for inp in slabs], n_images, rate, self.REFINE_GRID,
                                               int(self.REFINE_GRID_ITERS), float(self.REFINE_MAX_STEP),
@@ -572,7 +568,6 @@ class VideoAligner:
         H, W = parts[0].shape[1:]
         sel = _in.sample_mask(n_images, rate, res.skipped)
         mean0 = _q.mean_image(parts, sel)
-        self.affines = res.affines
         region = _q.valid_region(np.asarray(res.affines)[:n_images], H, W,
                                  taps=4 if self._interpolation_on() == "cubic" else 2)
         corr = _q.frame_correlations(parts, mean0, region)
@@ -623,6 +618,23 @@ class VideoAligner:
         return res
 
     # ------------------------------------------------------------- public API
+    def _begin(self, images, refine_supported: bool) -> None:
+        """What align_images and align_keypoints open with: the results of the switches reset and
+        every switch checked, before any work.  The order of the checks decides which of two
+        conflicting switches is named."""
+        self._interpolation_on(images)
+        self._reset_bidi()
+        self._bidi_on(images)
+        self._reset_quality()
+        self._quality_on(refine_supported)
+        self._reset_piecewise()
+        self._piecewise_on(images)
+        self._reset_fallback()
+        self._fallback_on(images)
+        self._reset_refine()
+        self._refine_on(images)
+        self._log_one_device()
+
     def align_images(
         self,
         images: np.ndarray,
@@ -641,23 +653,11 @@ class VideoAligner:
         With BIDI_PHASE on, the template frame is taken from the corrected stack; a
         ``masked_template`` is used as given (the caller corrects it, bidi.shift_rows).
         """
-        self._interpolation_on(images)
-        self._reset_bidi()
-        self._bidi_on(images)
-        self._reset_quality()
-        self._quality_on()
-        self._reset_piecewise()
-        self._piecewise_on(images)
-        self._reset_fallback()
-        self._fallback_on(images)
-        self._reset_refine()
-        self._refine_on(images)
-        self._log_one_device()
+        self._begin(images, refine_supported=True)
         self.logger.info(f"aligning {len(images)} frames with n_kp_global: {n_kp_global} and {detector_algorithm}")
         if not 0 <= self.TEMPLATE_FRAME_LOC <= 1:
             raise ValueError("`template_frame_loc` must be between 0 and 1")
         on_device = isinstance(images, torch.Tensor)
-        images_np = None if on_device else np.asarray(images)
         template_idx = None
         if masked_template is not None:
             template = _as_numpy(masked_template)
@@ -666,98 +666,14 @@ class VideoAligner:
             template = _as_numpy(images[template_idx])
             self.logger.info(f"no masked template provided. Using frame {template_idx} as template")
 
-        frame_downsample_rate = max(1, frame_rate // self.FRAME_SAMPLE_RATE)
-        devices = self._devices()
-        ranges = _md.split_frames(len(images), frame_downsample_rate, len(devices))
-        if len(ranges) > 1:
-            return self._align_images_split(images, template, n_kp_global, detector_algorithm, frame_downsample_rate,
-                                            patch, devices[:len(ranges)], ranges, template_idx)
-
+        rate = max(1, frame_rate // self.FRAME_SAMPLE_RATE)
         self.logger.info("normalizing frames...")
         t_start = time.time()
-        # VA:100-108 on the device: the stack is uploaded once (and reused by the warp),
-        # percentile and max-scaling run as HIP kernels; the uint8 copy comes back for the
-        # host detector.
-        assert (images.dtype == torch.uint16) if on_device else (images_np.dtype == np.uint16)  # VA:104
-        dev = self._device()
-        frames = images if on_device else torch.from_numpy(np.ascontiguousarray(images_np)).to(dev)
-        (frames,), template = self._bidi_source([frames], not on_device, template, template_idx)
-        brightest_px = self._get_brightest_px(frames)
-        u8_dev = self._max_scale_images(frames, None, brightest_px, np.uint8)[0]
-        _, template_i8 = self._max_scale_images(None, template, brightest_px, np.uint8)
-        detector = self.DETECTOR_CONSTRUCTOR_DICT[detector_algorithm]()
-        on_gpu = isinstance(detector, GpuOrbDetector) and frames.dim() == 3
-        if not on_gpu:
-            images_i8 = u8_dev.cpu().numpy()
-            images_sample, template = self._downsample(images_i8, template_i8, frame_downsample_rate,
-                                                       self.SPATIAL_DOWNSAMPLE_RATE)
-        self.logger.info(f"normalized frames in: {round(time.time() - t_start)} s")
-
-        self.logger.info("identifying keypoints...")
-        t_start = time.time()
-        if on_gpu:  # f1: detection of the whole stack on the device (f4: downsample there too)
-            sample_dev, tpl_dev = _pl.downsample_u8(u8_dev, torch.from_numpy(np.ascontiguousarray(template_i8)).to(dev)[None],
-                                                    frame_downsample_rate, self.SPATIAL_DOWNSAMPLE_RATE)
-            kt = stages.detect_orb(tpl_dev, detector.params)
-            kq = stages.detect_orb(sample_dev, detector.params)
-            n_t = int(kt.count.cpu()[0])
-            self._kp_template = kt.kp[0, :n_t].cpu().numpy()
-            self._des_template = kt.des[0, :n_t].cpu().numpy()
-            kp_q, des_q, q_off, q_off_host = stages.keypoints_csr(kq)
-            inp = _pl.SlabInputs(frames, kt.des[0, :n_t].contiguous(), kt.kp[0, :n_t].contiguous(), des_q, kp_q,
-                                 q_off, q_off_host)
-            self.logger.info(f"identified keypoints in: {round(time.time() - t_start)} s")
-
-            def detect_template(tpl_u16):  # as a masked_template enters: max-scale, downsample, detect
-                t8 = np.ascontiguousarray(self._max_scale_images(None, tpl_u16, brightest_px, np.uint8)[1])
-                t8 = torch.from_numpy(t8).to(dev)[None]
-                k = stages.detect_orb(_pl.downsample_u8(t8, t8, frame_downsample_rate, self.SPATIAL_DOWNSAMPLE_RATE)[1],
-                                      detector.params)
-                n = int(k.count.cpu()[0])
-                return k.kp[0, :n].cpu().numpy(), k.des[0, :n].cpu().numpy()
-
-            aligned, eu, skipped = self._align_inputs(inp, n_kp_global, frame_downsample_rate, patch,
-                                                      detect_template=detect_template)
-            return (aligned if on_device else aligned.cpu().numpy()), eu, skipped
-        detect_template = self._host_template_detector(detector, brightest_px, frame_downsample_rate)
-        kp_t, des_t = detector.detectAndCompute(template, None)
-        self._kp_template = np.array([p.pt for p in kp_t])
-        self._des_template = des_t
-        kp_list, des_list = [], []
-        for img in images_sample:
-            kq, dq = detector.detectAndCompute(img, None)
-            kp_list.append(np.array([p.pt for p in kq], dtype=np.float64).reshape(-1, 2))
-            des_list.append(np.asarray(dq, dtype=np.uint8).reshape(len(kq), -1))
-        self.logger.info(f"identified keypoints in: {round(time.time() - t_start)} s")
-        aligned, eu, skipped = self._align_detected(frames, self._kp_template, self._des_template, kp_list, des_list,
-                                                    n_kp_global, frame_downsample_rate, patch,
-                                                    detect_template=detect_template)
-        if not on_device:
-            aligned = aligned.cpu().numpy()
-        return aligned, eu, skipped
-
-    def _host_template_detector(self, detector, brightest_px, rate) -> Callable:
-        """template_u16 -> (kp, des) with a host (OpenCV-style) detector, the way a
-        masked_template enters align_images: max-scale, downsample, detectAndCompute."""
-        def detect_template(tpl_u16):
-            t8 = self._max_scale_images(None, tpl_u16, brightest_px, np.uint8)[1]
-            t8 = self._downsample(t8[None], t8, rate, self.SPATIAL_DOWNSAMPLE_RATE)[1]
-            kp_t, des_t = detector.detectAndCompute(t8, None)
-            return np.array([p.pt for p in kp_t]), des_t
-
-        return detect_template
-
-    def _align_images_split(self, images, template, n_kp_global, detector_algorithm, rate, patch, devices, ranges,
-                            template_idx=None):
-        """align_images with the stack split over several devices (kcmc_amd.multidevice):
-        each slab's frames uploaded to its device, the 99.99th percentile of the whole stack
-        from the summed per-device histograms, max-scaling and (GPU detector) detection per
-        device, then the split hot path."""
-        on_device = isinstance(images, torch.Tensor)
-        self.logger.info("normalizing frames...")
-        t_start = time.time()
+        # VA:100-108 on the device(s): each slab is uploaded once (and reused by the warp), the
+        # 99.99th percentile of the whole stack comes from the summed per-device histograms and
+        # the max-scaling runs per device; the uint8 copy comes back only for a host detector.
         assert (images.dtype == torch.uint16) if on_device else (np.asarray(images).dtype == np.uint16)  # VA:104
-        parts = _md.split_to_devices(images if on_device else np.asarray(images), ranges, devices)
+        parts, ranges = self._split(images, rate)
         parts, template = self._bidi_source(parts, not on_device, template, template_idx)
         brightest_px = stages.brightest_px(parts, self.IMAGE_NORM_MAX_PERCENTILE)
         u8_parts = []
@@ -772,35 +688,8 @@ class VideoAligner:
         self.logger.info("identifying keypoints...")
         t_start = time.time()
         cfg = self._config(n_kp_global, rate)
-        if on_gpu:  # f1 per device: each slab's sample frames detected where they live
-            tpl_u8 = np.ascontiguousarray(template_i8)
-            samples = []
-            for u in u8_parts:
-                with _md._on(u):
-                    samples.append(_pl.downsample_u8(u, torch.from_numpy(tpl_u8).to(u.device)[None], rate,
-                                                     self.SPATIAL_DOWNSAMPLE_RATE))
-            with _md._on(samples[0][1]):
-                kt = stages.detect_orb(samples[0][1], detector.params)
-            n_t = int(kt.count.cpu()[0])
-            self._kp_template = kt.kp[0, :n_t].cpu().numpy()
-            self._des_template = kt.des[0, :n_t].cpu().numpy()
-            slabs = []
-            for fr, (smp, _) in zip(parts, samples):
-                with _md._on(smp):
-                    kp_q, des_q, q_off, q_off_host = stages.keypoints_csr(stages.detect_orb(smp, detector.params))
-                dev = fr.device
-                slabs.append(_pl.SlabInputs(fr, torch.from_numpy(self._des_template).to(dev),
-                                            torch.from_numpy(self._kp_template).to(dev), des_q, kp_q, q_off, q_off_host))
-
-            def detect_template(tpl_u16):  # on the first slab's device, as the first template was
-                t8 = np.ascontiguousarray(self._max_scale_images(None, tpl_u16, brightest_px, np.uint8)[1])
-                with _md._on(u8_parts[0]):
-                    t8 = torch.from_numpy(t8).to(u8_parts[0].device)[None]
-                    k = stages.detect_orb(_pl.downsample_u8(t8, t8, rate, self.SPATIAL_DOWNSAMPLE_RATE)[1],
-                                          detector.params)
-                n = int(k.count.cpu()[0])
-                return k.kp[0, :n].cpu().numpy(), k.des[0, :n].cpu().numpy()
-        else:
+        out = images.device if on_device else None
+        if not on_gpu:
             detect_template = self._host_template_detector(detector, brightest_px, rate)
             images_i8 = np.concatenate([u.cpu().numpy() for u in u8_parts])
             images_sample, template = self._downsample(images_i8, template_i8, rate, self.SPATIAL_DOWNSAMPLE_RATE)
@@ -812,29 +701,86 @@ class VideoAligner:
                 kq, dq = detector.detectAndCompute(img, None)
                 kp_list.append(np.array([p.pt for p in kq], dtype=np.float64).reshape(-1, 2))
                 des_list.append(np.asarray(dq, dtype=np.uint8).reshape(len(kq), -1))
-            kp_flat, des_flat, q_off = self._csr(kp_list, des_list, np.asarray(des_t).shape[1])
-            slabs = _md.make_slabs(parts, ranges, np.asarray(des_t, np.uint8), self._kp_template, kp_flat, des_flat,
-                                   q_off)
+            self.logger.info(f"identified keypoints in: {round(time.time() - t_start)} s")
+            return self._align_detected(parts, ranges, self._kp_template, np.asarray(des_t, np.uint8), kp_list,
+                                        des_list, cfg, patch, out, detect_template)
+        # f1 per device: each slab's sample frames detected where they live (f4: downsampled there too)
+        tpl_u8 = np.ascontiguousarray(template_i8)
+        samples = []
+        for u in u8_parts:
+            with _md._on(u):
+                samples.append(_pl.downsample_u8(u, torch.from_numpy(tpl_u8).to(u.device)[None], rate,
+                                                 self.SPATIAL_DOWNSAMPLE_RATE))
+        with _md._on(samples[0][1]):
+            kt = stages.detect_orb(samples[0][1], detector.params)
+        n_t = int(kt.count.cpu()[0])
+        self._kp_template = kt.kp[0, :n_t].cpu().numpy()
+        self._des_template = kt.des[0, :n_t].cpu().numpy()
+        slabs = []
+        for fr, (smp, _) in zip(parts, samples):
+            with _md._on(smp):
+                kp_q, des_q, q_off, q_off_host = stages.keypoints_csr(stages.detect_orb(smp, detector.params))
+            dev = fr.device
+            slabs.append(_pl.SlabInputs(fr, torch.from_numpy(self._des_template).to(dev),
+                                        torch.from_numpy(self._kp_template).to(dev), des_q, kp_q, q_off, q_off_host))
         self.logger.info(f"identified keypoints in: {round(time.time() - t_start)} s")
-        return self._finish_split(slabs, ranges, cfg, patch, images.device if on_device else None, detect_template)
 
-    def _finish_split(self, slabs, ranges, cfg, patch, out_device, detect_template=None):
+        def detect_template(tpl_u16):  # as a masked_template enters, on the first slab's device
+            t8 = np.ascontiguousarray(self._max_scale_images(None, tpl_u16, brightest_px, np.uint8)[1])
+            with _md._on(u8_parts[0]):
+                t8 = torch.from_numpy(t8).to(u8_parts[0].device)[None]
+                k = stages.detect_orb(_pl.downsample_u8(t8, t8, rate, self.SPATIAL_DOWNSAMPLE_RATE)[1],
+                                      detector.params)
+            n = int(k.count.cpu()[0])
+            return k.kp[0, :n].cpu().numpy(), k.des[0, :n].cpu().numpy()
+
+        return self._finish(slabs, ranges, cfg, patch, out, detect_template)
+
+    def _split(self, images, rate: int):
+        """(parts, ranges): the stack's slabs on the devices of the hot path, one per device that
+        gets a sample frame (kcmc_amd.multidevice; one device: a list of one), and their frame
+        ranges.  An empty stack is one empty slab."""
+        devices = self._devices()
+        ranges = _md.split_frames(len(images), rate, len(devices)) or [_md.SlabRange(0, 0, 0, 0)]
+        frames = images if isinstance(images, torch.Tensor) else np.asarray(images)
+        return _md.split_to_devices(frames, ranges, devices[:len(ranges)]), ranges
+
+    def _host_template_detector(self, detector, brightest_px, rate) -> Callable:
+        """template_u16 -> (kp, des) with a host (OpenCV-style) detector, the way a
+        masked_template enters align_images: max-scale, downsample, detectAndCompute."""
+        def detect_template(tpl_u16):
+            t8 = self._max_scale_images(None, tpl_u16, brightest_px, np.uint8)[1]
+            t8 = self._downsample(t8[None], t8, rate, self.SPATIAL_DOWNSAMPLE_RATE)[1]
+            kp_t, des_t = detector.detectAndCompute(t8, None)
+            return np.array([p.pt for p in kp_t]), des_t
+
+        return detect_template
+
+    def _finish(self, slabs, ranges, cfg, patch, out, detect_template=None):
+        """The tail of align_images and align_keypoints: the hot path over the slabs -- align_slab
+        for one (the only one with the piecewise-rigid mode), align_split for several -- with the
+        fallback, the refinement and the template passes around it; then the results.  ``out``:
+        the device the aligned stack is returned on, None for a numpy array."""
         self.logger.info("generating keypoint consensus...")
         t_start = time.time()
-        # the metrics read the aligned slabs where they are, before they are gathered
         n_images, rate = ranges[-1].f1, int(cfg.frame_downsample_rate)
-        hot = self._with_fallback(lambda: _md.align_split(slabs, ranges, cfg, logger=self.logger), slabs, n_images,
-                                  rate)
-        hot = self._with_refine(hot, slabs, n_images, rate)
+        if len(slabs) == 1:
+            hot = lambda: _pl.align_slab(slabs[0], cfg, logger=self.logger)  # noqa: E731
+        else:
+            hot = lambda: _md.align_split(slabs, ranges, cfg, logger=self.logger)  # noqa: E731
+        hot = self._with_refine(self._with_fallback(hot, slabs, n_images, rate), slabs, n_images, rate)
+        # the metrics read the aligned slabs where they are, before they are gathered
         res = self._run_passes(hot, slabs, n_images, rate, detect_template)
         self.interpolated_idxs = res.interpolated
-        if self._interpolation_on() == "cubic":  # the maps the frames were resampled with
-            self.affines = res.affines
         self.logger.info(f"aligned frames in: {round(time.time() - t_start)} s")
-        aligned = _md.gather_aligned(res, out_device)
+        self._take_piecewise(res)
+        self.affines = res.affines  # the maps the returned frames were resampled with, after every pass
+        aligned = res.aligned if len(slabs) == 1 else _md.gather_aligned(res, out)
         if patch is not None:
             x_start, y_start, width, height = patch
             aligned = aligned[:, x_start:x_start + width, y_start:y_start + height]
+        if isinstance(aligned, torch.Tensor):  # one slab: the result itself, or only its patch copied
+            aligned = aligned.cpu().numpy() if out is None else aligned.to(out)
         return aligned, res.euclidean, res.skipped
 
     @staticmethod
@@ -859,76 +805,24 @@ class VideoAligner:
         """The hot path with precomputed keypoints: per SAMPLE frame
         (images[::max(1, frame_rate // FRAME_SAMPLE_RATE)]) keypoint coordinates [n, 2]
         and uint8 descriptors [n, D]; template keypoints/descriptors likewise."""
-        self._interpolation_on(images)
-        self._reset_bidi()
-        self._bidi_on(images)
-        self._reset_quality()
-        self._quality_on(refine_supported=False)
-        self._reset_piecewise()
-        self._piecewise_on(images)
-        self._reset_fallback()
-        self._fallback_on(images)
-        self._reset_refine()
-        self._refine_on(images)
-        self._log_one_device()
+        self._begin(images, refine_supported=False)
         self._kp_template = np.asarray(kp_template, dtype=np.float64).reshape(-1, 2)
         self._des_template = np.asarray(des_template, dtype=np.uint8)
         rate = max(1, frame_rate // self.FRAME_SAMPLE_RATE)
-        return self._align_detected(images, self._kp_template, self._des_template, list(kp_query), list(des_query),
-                                    n_kp_global, rate, patch, bidi=True)
+        on_device = isinstance(images, torch.Tensor)
+        parts, ranges = self._split(images, rate)
+        parts = self._bidi_correct(parts, not on_device)  # the caller's frames: corrected here
+        return self._align_detected(parts, ranges, self._kp_template, self._des_template, list(kp_query),
+                                    list(des_query), self._config(n_kp_global, rate), patch,
+                                    images.device if on_device else None)
 
-    def _align_detected(self, images, kp_template, des_template, kp_list, des_list, n_kp_global, rate, patch,
-                        detect_template=None, bidi: bool = False):
-        """``bidi``: the frames are the caller's and take the phase correction here (align_images
-        has applied it before it detects)."""
-        to_host = not isinstance(images, torch.Tensor)
+    def _align_detected(self, parts, ranges, kp_template, des_template, kp_list, des_list, cfg, patch, out,
+                        detect_template=None):
+        """_finish over the slabs of host-side keypoints: one [n, 2] and one [n, D] array per sample
+        frame of the whole stack, cut per slab (multidevice.make_slabs)."""
         kp_flat, des_flat, q_off = self._csr(kp_list, des_list, des_template.shape[1])
-        devices = self._devices()
-        ranges = _md.split_frames(len(images), rate, len(devices))
-        if len(ranges) > 1:  # every device its slab of frames (kcmc_amd.multidevice)
-            parts = _md.split_to_devices(images if not to_host else np.asarray(images), ranges, devices)
-            if bidi:
-                parts = self._bidi_correct(parts, to_host)
-            slabs = _md.make_slabs(parts, ranges, des_template, kp_template, kp_flat, des_flat, q_off)
-            return self._finish_split(slabs, ranges, self._config(n_kp_global, rate), patch,
-                                      None if to_host else images.device, detect_template)
-        dev = torch.device("cuda", devices[0])
-        frames = torch.from_numpy(np.ascontiguousarray(images)).to(dev) if to_host else images.contiguous()
-        if bidi:
-            frames = self._bidi_correct([frames], to_host)[0]
-        inp = _pl.SlabInputs(
-            frames=frames,
-            des_tpl=torch.from_numpy(np.ascontiguousarray(des_template, np.uint8)).to(dev),
-            kp_tpl=torch.from_numpy(np.ascontiguousarray(kp_template, np.float64)).to(dev),
-            des_q=torch.from_numpy(np.ascontiguousarray(des_flat)).to(dev),
-            kp_q=torch.from_numpy(np.ascontiguousarray(kp_flat).reshape(-1, 2)).to(dev),
-            q_off=torch.from_numpy(q_off).to(dev),
-            q_off_host=q_off,
-        )
-        return self._align_inputs(inp, n_kp_global, rate, patch, to_host=to_host, detect_template=detect_template)
-
-    def _align_inputs(self, inp, n_kp_global, rate, patch, to_host: bool = False, detect_template=None):
-        cfg = self._config(n_kp_global, rate)
-        self.logger.info("generating keypoint consensus...")
-        t_start = time.time()
-        n_images = inp.frames.shape[0]
-        hot = self._with_fallback(lambda: _pl.align_slab(inp, cfg, logger=self.logger), [inp], n_images, rate)
-        hot = self._with_refine(hot, [inp], n_images, rate)
-        res = self._run_passes(hot, [inp], n_images, rate, detect_template)
-        self.interpolated_idxs = res.interpolated
-        if self._interpolation_on() == "cubic":  # the maps the frames were resampled with
-            self.affines = res.affines
-        self.logger.info(f"aligned frames in: {round(time.time() - t_start)} s")
-        self._take_piecewise(res)
-        aligned = res.aligned
-        if patch is not None:
-            x_start, y_start, width, height = patch
-            x_end = x_start + width
-            y_end = y_start + height
-            aligned = aligned[:, x_start:x_end, y_start:y_end]
-        if to_host:
-            aligned = aligned.cpu().numpy()
-        return aligned, res.euclidean, res.skipped
+        slabs = _md.make_slabs(parts, ranges, des_template, kp_template, kp_flat, des_flat, q_off)
+        return self._finish(slabs, ranges, cfg, patch, out, detect_template)
 
     # ------------------------------------------------ per-frame helpers (VA:160-458)
     @classmethod
@@ -954,14 +848,7 @@ class VideoAligner:
         bits = m.keep_bits.cpu().numpy().view(np.uint32)[0]
         kept = [k for k in range(n_tpl) if (bits[k >> 5] >> (k & 31)) & 1]
         c = m.counts.cpu().numpy()[0]
-        log_str = (
-            f"frame {i}:\n"
-            f"\t{int(c[0])} unfiltered features identified\n"
-            f"\t{int(c[1])} matches identified between frame and template\n"
-            f"\t{int(c[2])} matches after feature-space ratio filter\n"
-            f"\t{int(c[3])} matches after distance-based outlier rejection"
-        )
-        return set(kept), m.kp_ordered.cpu().numpy()[0], log_str
+        return set(kept), m.kp_ordered.cpu().numpy()[0], _pl.frame_counts_text(i, c)
 
     def _get_consensus_kps(self, kp_idxs_list: List[set], n_frames: int, n_kp_global: int) -> Set[int]:
         """VA:224-249: the n_kp_global most frequently matched template keypoints."""

@@ -236,7 +236,6 @@ def test_align_images_multiscale_similarity_on_a_zooming_stack(dev):
     class Zoom(VideoAligner):
         RANSAC_MODEL = "similarity"
         DEVICES = [0]
-        QUALITY_METRICS = True  # keeps the maps of the pass in .affines
 
     imgs = np.stack([(pyr.zoom_frame(z, s, noise_seed=i) * 256.0).astype(np.uint16)
                      for i, (z, s) in enumerate(zip(ZOOMS, SHIFTS))])
