@@ -16,16 +16,11 @@
 //   any other pixel: sum = 0, then sum += p_ij for i = 0..3 and within that j = 0..3
 // and the output is saturate_cast<ushort>(sum) (sat_u16).
 //
-// Layout: the field warp's (warp_field.hip) -- 128 x 56 (or 64) output tiles, one workgroup per
-// tile, one output row per wave and pass, lane l the pixels 2l, 2l + 1.  A plan kernel (one
-// thread per tile) inverts the map and bounds the tile's source box: the affine box
-// (warp.hip source_box) widened to the footprint, one more column and row on the low side and
-// two on the high side.  Boxes within the staging budget are staged in LDS (zeros outside the
-// image: BORDER_CONSTANT), boxes that miss the image store zeros, every other tile gathers from
-// global memory with range-checked taps.  A staged tile whose box lies inside the image holds
-// interior pixels only and makes the interior sum alone; a tile that touches the border makes
-// both sums from the same sixteen products and selects per pixel, as the gather path does, so
-// the two paths give the same bits.
+// Layout, plan modes and staging: the shared tile skeleton (warp_tile.h).  The source box is
+// the affine box widened to the footprint, one more column and row on the low side and two on
+// the high side.  A staged tile whose box lies inside the image holds interior pixels only and
+// makes the interior sum alone; a tile that touches the border makes both sums from the same
+// sixteen products and selects per pixel, as the gather path does, so the paths give the same bits.
 //
 // LDS: a lane reads its taps with 16-bit reads.  One read instruction takes the same tap (i, j)
 // of 64 neighbouring pixel pairs, so the lanes of a 32-lane group read consecutive dwords of a
@@ -35,22 +30,10 @@
 // 512 bytes of LDS behind the box.  A lane's two pixels share twelve of their sixteen taps under
 // near-identity maps (cubic_rows), and their arithmetic runs on packed fp32, one element each.
 // Bound by VALU issue at about three times the bilinear warp's time (DESIGN K3c).
-#include <climits>
-
-#include "kcmc_internal.h"
-#include "warp_common.h"
+#include "warp_tile.h"
 
 namespace kcmc {
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kTileW = 128;      // output columns per tile (64 lanes x 2 pixels)
-constexpr int kMaxPitch = 256;   // staged row length limit (32 x 16-byte chunks)
-constexpr int kLdsElems = 10240; // uint16 staging budget per box (20 KB)
-constexpr int kRowPasses = 9;    // staging passes of 8 rows x 32 chunks (box rows <= 72)
-
-// the affine warp's tile-height rule (warp.hip use_tile64)
-inline bool use_tile64(int H) { return H % 64 == 0 && H % 56 != 0; }
 
 // c_j(f) 2^17 for f = 0..31: ((A(t+1) - 5A)(t+1) + 8A)(t+1) - 4A, ((A+2)t - (A+3))t^2 + 1,
 // the same at 1 - t, and 1 - the three, with A = -3/4 and t = f / 32 (exact: t has 5 bits).
@@ -67,54 +50,19 @@ __constant__ int kCubicNum[32][4] = {
     {-2025, 19535, 124497, -10935}, {-1344, 15040, 126784, -9408}, {-783, 10809, 128615, -7569},
     {-360, 6872, 129960, -5400},  {-93, 3259, 130789, -2883}};
 
-struct CubicPlan {
-  int mode;        // 0: staged in LDS, 1: zeros, 2: direct gather
-  int ax0, sy0;    // first staged column (multiple of 8) / row
-  int pitch_rows;  // pitch | rows << 16 | (box inside the image) << 31
-};
-
 // ------------------------------------------------------------------------------- plan
-// Thread t < tiles: the tile's plan (and, for the frame's first tile, the inverted map).
+// Thread t < tiles: the tile's plan.  The box: the affine box widened to the 4 x 4 footprint,
+// taps sx - 1 .. sx + 2.
 template <int TILE_H>
 __global__ __launch_bounds__(256) void cubic_plan_kernel(const double* __restrict__ Mall, int n_frames, int H, int W,
                                                          int inverse_map, int ntx, int nty,
-                                                         CubicPlan* __restrict__ plan, double* __restrict__ minv) {
+                                                         TilePlan* __restrict__ plan, double* __restrict__ minv) {
   const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
   if (t >= (long long)ntx * nty * n_frames) return;
-  const int f = (int)(t / (ntx * nty)), t2 = (int)(t - (long long)f * ntx * nty);
-  const int xb = (t2 % ntx) * kTileW, yb = (t2 / ntx) * TILE_H;
-  double M[6];
-  load_map(Mall, f, inverse_map, M);
-  if (t2 == 0)
-    for (int k = 0; k < 6; ++k) minv[6 * (size_t)f + k] = M[k];
-  // the affine box in 1/1024 px (warp.hip source_box: monotone in x and in y), widened to the
-  // 4 x 4 footprint: taps sx - 1 .. sx + 2
-  const int xl = min(xb + kTileW, W) - 1, yl = min(yb + TILE_H, H) - 1;
-  const long long a0 = cv_round(M[0] * xb * 1024), a1 = cv_round(M[0] * xl * 1024);
-  const long long b0 = cv_round(M[3] * xb * 1024), b1 = cv_round(M[3] * xl * 1024);
-  const long long x0 = cv_round((M[1] * yb + M[2]) * 1024) + 16, x1 = cv_round((M[1] * yl + M[2]) * 1024) + 16;
-  const long long y0 = cv_round((M[4] * yb + M[5]) * 1024) + 16, y1 = cv_round((M[4] * yl + M[5]) * 1024) + 16;
-  const long long sx0 = ((min(x0, x1) + min(a0, a1)) >> 10) - 1, sx1 = ((max(x0, x1) + max(a0, a1)) >> 10) + 2;
-  const long long sy0 = ((min(y0, y1) + min(b0, b1)) >> 10) - 1, sy1 = ((max(y0, y1) + max(b0, b1)) >> 10) + 2;
-  const long long lim = 30000;  // keep clear of saturate_cast<short> on coordinates
-  const bool small = sx0 > -lim && sx1 < lim && sy0 > -lim && sy1 < lim;
-  const long long ax0 = (sx0 >> 3) << 3;
-  const long long pitch = ((sx1 - ax0 + 1) + 7) & ~7ll;
-  const long long rows = sy1 - sy0 + 1;
-  CubicPlan p;
-  p.mode = 2;
-  p.ax0 = p.sy0 = p.pitch_rows = 0;
-  if (small && (sx1 < 0 || sx0 > W - 1 || sy1 < 0 || sy0 > H - 1)) {
-    p.mode = 1;
-  } else if (small && pitch <= kMaxPitch && rows <= 8 * kRowPasses && pitch * rows <= kLdsElems) {
-    p.mode = 0;
-    p.ax0 = (int)ax0;
-    p.sy0 = (int)sy0;
-    const bool inside = sx0 >= 0 && sx1 <= W - 1 && sy0 >= 0 && sy1 <= H - 1;
-    p.pitch_rows = (int)pitch | ((int)rows << 16) | (inside ? INT_MIN : 0);
-  }
-  if (map_has_nan(M, 6)) p.mode = 1;  // a NaN map (a frame RANSAC could not fit) warps to zeros
-  plan[t] = p;
+  const PlanTile p = plan_tile<TILE_H>(t, Mall, inverse_map, H, W, ntx, nty, minv);
+  const Box1024 b = affine_box(p.M, p.xb, p.yb, p.xl, p.yl);
+  plan[t] = classify_box((b.x0 >> 10) - 1, (b.x1 >> 10) + 2, (b.y0 >> 10) - 1, (b.y1 >> 10) + 2, H, W, true,
+                         map_has_nan(p.M, 6));
 }
 
 // ------------------------------------------------------------------------------- pixel
@@ -152,8 +100,7 @@ __device__ __forceinline__ void cubic_sum2(const f32x2 (&v)[4][4], const f32x2 (
 // ------------------------------------------------------------------------------- tiles
 // Output rows of one tile on one path (0: staged box inside the image, 1: zeros, 2: direct
 // gather, 3: staged box that touches the border).  Wave w makes rows w, w + 4, ...; lane l the
-// pixels x = xb + 2l, xb + 2l + 1.  Columns past the frame edge reuse the last valid column's
-// coordinates so that their (never stored) taps stay inside the box.
+// pixels x = xb + 2l, xb + 2l + 1.
 template <int TILE_H, int MODE>
 __device__ __forceinline__ void cubic_rows(const uint16_t* stile, const float (*wtab)[4], int pitch, int ax0, int sy0,
                                            const uint16_t* __restrict__ S, uint16_t* __restrict__ Dst, int H, int W,
@@ -251,75 +198,31 @@ __device__ __forceinline__ void cubic_rows(const uint16_t* stile, const float (*
 
 // no-unaligned-access-mode: keeps adjacent 16-bit tap reads from being fused into one 4-byte
 // LDS read at a 2-byte-aligned address (warp.hip).
-// vec_ok: W % 8 == 0 and src 16-byte aligned (16-byte staging loads); pair_ok: W even and dst
-// 4-byte aligned (one 4-byte store per lane).
 template <int TILE_H>
 __global__ __launch_bounds__(kThreads) __attribute__((target("no-unaligned-access-mode"))) void warp_cubic_u16_kernel(
-    const uint16_t* __restrict__ src, uint16_t* __restrict__ dst, const CubicPlan* __restrict__ plan,
+    const uint16_t* __restrict__ src, uint16_t* __restrict__ dst, const TilePlan* __restrict__ plan,
     const double* __restrict__ minv, int H, int W, int vec_ok, int pair_ok) {
   __shared__ __attribute__((aligned(16))) uint16_t stile[kLdsElems + 8];  // + the fifth column's overhang
   __shared__ float wtab[32][4];  // the 1-D weights
-  const int ntx = gridDim.x, nty = gridDim.y;
-  const int tile = xcd_remap(blockIdx.x + ntx * (blockIdx.y + nty * blockIdx.z), ntx * nty * gridDim.z);
-  const int f = tile / (ntx * nty);
-  const int t2 = tile - f * ntx * nty;
-  const int xb = (t2 % ntx) * kTileW, yb = (t2 / ntx) * TILE_H;
-  const int tid = threadIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-  const uint16_t* S = src + (size_t)f * H * W;
-  uint16_t* Dst = dst + (size_t)f * H * W;
-
-  const CubicPlan tp = plan[tile];
-  const int mode = tp.mode, ax0 = tp.ax0, sy0 = tp.sy0;
-  const int pitch = tp.pitch_rows & 0xffff, rows = (tp.pitch_rows >> 16) & 0x7fff;
-  const bool inside = tp.pitch_rows < 0;
+  const TileId t = tile_decode<TILE_H>();
+  const int tid = threadIdx.x, xb = t.xb, yb = t.yb, wave = t.wave, lane = t.lane;
+  const uint16_t* S = src + (size_t)t.f * H * W;
+  uint16_t* Dst = dst + (size_t)t.f * H * W;
+  const TilePlan tp = plan[t.tile];
+  const int mode = tp.mode, ax0 = tp.ax0, sy0 = tp.sy0, pitch = tp.pitch();
   const bool vec_stage = mode == 0 && vec_ok;
 
-  // staging loads first: chunk c = tid & 31 of box row tid >> 5 + 8 k; with W % 8 == 0 a
-  // 16-byte chunk is entirely inside or entirely outside the image (zeros)
   uint4 chunk[kRowPasses];
-  const int cpr = pitch >> 3, sc = tid & 31, sr = tid >> 5;
-  if (vec_stage) {
-    const int cx = ax0 + 8 * sc;
-    const bool col_ok = sc < cpr && cx >= 0 && cx < W;
-#pragma unroll
-    for (int k = 0; k < kRowPasses; ++k) {
-      const int r = sr + 8 * k, cy = sy0 + r;
-      chunk[k] = make_uint4(0u, 0u, 0u, 0u);
-      if (r < rows && col_ok && (unsigned)cy < (unsigned)H)
-        chunk[k] = *reinterpret_cast<const uint4*>(S + (size_t)cy * W + cx);
-    }
-  }
+  stage_load(S, tp, H, W, vec_stage, chunk);
   if (tid < 128) wtab[tid >> 2][tid & 3] = (float)kCubicNum[tid >> 2][tid & 3] * 0x1p-17f;  // exact
-  // the lane's two columns and, in lane i < TILE_H / 4, the origins of the wave's i-th row;
-  // for a staged tile the box origin is folded into the row origins (a multiple of 1024)
-  const double* M = minv + 6 * (size_t)f;
-  int ad[2], bd[2];
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    const int x = min(xb + 2 * lane + q, W - 1);
-    ad[q] = cv_round(M[0] * x * 1024);
-    bd[q] = cv_round(M[3] * x * 1024);
-  }
-  const int yl = yb + wave + 4 * min(lane, TILE_H / 4 - 1);
-  const int X0v = cv_round((M[1] * yl + M[2]) * 1024) + 16 - (mode == 0 ? ax0 : 0) * 1024;
-  const int Y0v = cv_round((M[4] * yl + M[5]) * 1024) + 16 - (mode == 0 ? sy0 : 0) * 1024;
-  if (vec_stage) {
-#pragma unroll
-    for (int k = 0; k < kRowPasses; ++k) {
-      const int r = sr + 8 * k;
-      if (r < rows && sc < cpr) *reinterpret_cast<uint4*>(&stile[r * pitch + 8 * sc]) = chunk[k];
-    }
-  } else if (mode == 0) {  // element-wise staging (W % 8 != 0 or an unaligned slab)
-    for (int q = tid; q < rows * pitch; q += kThreads) {
-      const int r = q / pitch, e = q - r * pitch;
-      const int cy = sy0 + r, cx = ax0 + e;
-      stile[q] = ((unsigned)cy < (unsigned)H && (unsigned)cx < (unsigned)W) ? S[(size_t)cy * W + cx] : (uint16_t)0;
-    }
-  }
+  const double* M = minv + 6 * (size_t)t.f;
+  int ad[2], bd[2], X0v, Y0v;
+  lane_columns(M, xb, lane, W, ad, bd);
+  row_origins<TILE_H>(M, t, tp, X0v, Y0v);
+  stage_commit(stile, S, tp, H, W, vec_stage, chunk);
   __syncthreads();
   // one row loop per path (a path-uniform branch inside the loop drains the stores every row)
-  if (mode == 0 && inside)
+  if (mode == 0 && tp.inside())
     cubic_rows<TILE_H, 0>(stile, wtab, pitch, ax0, sy0, S, Dst, H, W, xb, yb, wave, lane, ad, bd, X0v, Y0v, pair_ok);
   else if (mode == 0)
     cubic_rows<TILE_H, 3>(stile, wtab, pitch, ax0, sy0, S, Dst, H, W, xb, yb, wave, lane, ad, bd, X0v, Y0v, pair_ok);
@@ -329,22 +232,6 @@ __global__ __launch_bounds__(kThreads) __attribute__((target("no-unaligned-acces
     cubic_rows<TILE_H, 2>(stile, wtab, pitch, ax0, sy0, S, Dst, H, W, xb, yb, wave, lane, ad, bd, X0v, Y0v, pair_ok);
 }
 
-// Workspace layout: minv [F, 6] f64, plan [tiles].
-template <int TILE_H>
-void launch_cubic(const uint16_t* src, uint16_t* dst, const double* M, int n_frames, int H, int W, int inverse_map,
-                  void* ws, hipStream_t s) {
-  const int ntx = ceil_div(W, kTileW), nty = ceil_div(H, TILE_H);
-  const long long tiles = (long long)ntx * nty * n_frames;
-  double* minv = static_cast<double*>(ws);
-  CubicPlan* plan = reinterpret_cast<CubicPlan*>(minv + 6 * (size_t)n_frames);
-  hipLaunchKernelGGL((cubic_plan_kernel<TILE_H>), dim3((unsigned)((tiles + 255) / 256)), dim3(256), 0, s, M, n_frames,
-                     H, W, inverse_map, ntx, nty, plan, minv);
-  const int vec_ok = (W & 7) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0;
-  const int pair_ok = (W & 1) == 0 && (reinterpret_cast<uintptr_t>(dst) & 3) == 0;
-  hipLaunchKernelGGL((warp_cubic_u16_kernel<TILE_H>), dim3(ntx, nty, n_frames), dim3(kThreads), 0, s, src, dst, plan,
-                     minv, H, W, vec_ok, pair_ok);
-}
-
 }  // namespace
 }  // namespace kcmc
 
@@ -352,29 +239,19 @@ using namespace kcmc;
 
 extern "C" int kcmc_warp_affine_cubic_u16(kcmc_ctx* ctx, const uint16_t* src, uint16_t* dst, const double* M,
                                           int n_frames, int H, int W, int C, int inverse_map, kcmc_stream_t stream) {
-  if (!ctx) return fail(KCMC_EINVAL, "kcmc_warp_affine_cubic_u16: ctx is NULL");
-  if (n_frames < 0) return fail(KCMC_EINVAL, "kcmc_warp_affine_cubic_u16: negative n_frames");
-  if (H < 1 || W < 1) return fail(KCMC_EINVAL, "kcmc_warp_affine_cubic_u16: H, W must be >= 1");
-  if (C == 3 || C == 4)
-    return fail(KCMC_EUNSUPPORTED, "kcmc_warp_affine_cubic_u16: grayscale only in this version (C must be 1)");
-  if (C != 1) return fail(KCMC_EINVAL, "kcmc_warp_affine_cubic_u16: C must be 1");
-  if (n_frames == 0) return KCMC_OK;
-  if (!src || !dst || !M) return fail(KCMC_EINVAL, "kcmc_warp_affine_cubic_u16: NULL pointer");
-  if (src == dst) return fail(KCMC_EINVAL, "kcmc_warp_affine_cubic_u16: in-place warp is not supported");
-  if (H > 32767 || W > 32767) return fail(KCMC_EUNSUPPORTED, "kcmc_warp_affine_cubic_u16: H, W must be < 32768");
-  if (n_frames > 65535) return fail(KCMC_EUNSUPPORTED, "kcmc_warp_affine_cubic_u16: at most 65535 frames per call");
-  const bool t64 = use_tile64(H);
-  const long long tiles = (long long)ceil_div(W, kTileW) * ceil_div(H, t64 ? 64 : 56) * n_frames;
-  if (tiles >= (1ll << 31)) return fail(KCMC_EUNSUPPORTED, "kcmc_warp_affine_cubic_u16: too many tiles in one call");
   hipStream_t s = (hipStream_t)stream;
-  void* ws = nullptr;
-  const size_t wsb = (size_t)n_frames * 6 * sizeof(double) + (size_t)tiles * sizeof(CubicPlan);
-  KCMC_TRY(workspace_alloc(ctx, &ws, wsb, s));
-  if (t64)
-    launch_cubic<64>(src, dst, M, n_frames, H, W, inverse_map, ws, s);
-  else
-    launch_cubic<56>(src, dst, M, n_frames, H, W, inverse_map, ws, s);
-  const int rc = launch_check("warp_cubic_u16_kernel");
-  KCMC_TRY(workspace_free(ctx, ws, s, wsb));
-  return rc;
+  return run_tile_warp(
+      "kcmc_warp_affine_cubic_u16", "warp_cubic_u16_kernel", ctx, src, dst, M != nullptr, n_frames, H, W, 0, s,
+      [&] {
+        if (C == 3 || C == 4)
+          return fail(KCMC_EUNSUPPORTED, "kcmc_warp_affine_cubic_u16: grayscale only in this version (C must be 1)");
+        return C != 1 ? fail(KCMC_EINVAL, "kcmc_warp_affine_cubic_u16: C must be 1") : (int)KCMC_OK;
+      },
+      [&](auto th, const TileLaunch& l) {
+        constexpr int TILE_H = decltype(th)::value;
+        hipLaunchKernelGGL((cubic_plan_kernel<TILE_H>), dim3((unsigned)((l.tiles + 255) / 256)), dim3(256), 0, s, M,
+                           n_frames, H, W, inverse_map, l.ntx, l.nty, l.plan, l.minv);
+        hipLaunchKernelGGL((warp_cubic_u16_kernel<TILE_H>), dim3(l.ntx, l.nty, n_frames), dim3(kThreads), 0, s, src,
+                           dst, l.plan, l.minv, H, W, l.vec_ok, l.pair_ok);
+      });
 }

@@ -610,6 +610,31 @@ def check_interpolation(interpolation) -> str:
     return interpolation
 
 
+def _warp_args(frames: torch.Tensor, dims, dims_msg: str, maps, out: Optional[torch.Tensor]):
+    """The argument checks of the u16 warps, in the order their errors are raised; returns
+    (device, out).  dims: the frame ranks allowed; maps: (tensor, name, dtype, shape behind F),
+    a str in the shape a free extent."""
+    dev = _device_of(frames)
+    if frames.dtype != torch.uint16:
+        raise TypeError(f"frames: expected torch.uint16, got {frames.dtype}")
+    if frames.dim() not in dims:
+        raise ValueError(dims_msg)
+    _require(frames, "frames", torch.uint16, dev)
+    for t, name, dtype, tail in maps:
+        _require(t, name, dtype, dev, 1 + len(tail))
+    for t, name, _, tail in maps:
+        want = (frames.shape[0], *tail)
+        if any(not isinstance(w, str) and w != n for w, n in zip(want, t.shape)):
+            raise ValueError(f"{name} must be [{', '.join(map(str, want))}], got {tuple(t.shape)}")
+    if out is None:
+        out = torch.empty_like(frames)
+    else:
+        _require(out, "out", torch.uint16, dev)
+        if out.shape != frames.shape:
+            raise ValueError("out must have the shape of frames")
+    return dev, out
+
+
 def warp_affine_u16(frames: torch.Tensor, affines: torch.Tensor, out: Optional[torch.Tensor] = None,
                     inverse_map: bool = False, stream: Optional[int] = None,
                     interpolation: str = "linear") -> torch.Tensor:
@@ -622,23 +647,10 @@ def warp_affine_u16(frames: torch.Tensor, affines: torch.Tensor, out: Optional[t
     check_interpolation(interpolation)
     if interpolation == "cubic" and frames.dim() == 4:
         raise NotImplementedError("interpolation='cubic' is grayscale only: frames must be [F, H, W]")
-    dev = _device_of(frames)
-    if frames.dtype != torch.uint16:
-        raise TypeError(f"frames: expected torch.uint16, got {frames.dtype}")
-    if frames.dim() not in (3, 4):
-        raise ValueError("frames must be [F, H, W] or [F, H, W, C]")
-    _require(frames, "frames", torch.uint16, dev)
-    _require(affines, "affines", torch.float64, dev, 3)
+    dev, out = _warp_args(frames, (3, 4), "frames must be [F, H, W] or [F, H, W, C]",
+                          [(affines, "affines", torch.float64, (2, 3))], out)
     F, H, W = frames.shape[:3]
     C = 1 if frames.dim() == 3 else frames.shape[3]
-    if affines.shape != (F, 2, 3):
-        raise ValueError(f"affines must be [{F}, 2, 3], got {tuple(affines.shape)}")
-    if out is None:
-        out = torch.empty_like(frames)
-    else:
-        _require(out, "out", torch.uint16, dev)
-        if out.shape != frames.shape:
-            raise ValueError("out must have the shape of frames")
     L = _lib.load()
     entry = L.kcmc_warp_affine_cubic_u16 if interpolation == "cubic" else L.kcmc_warp_affine_u16
     _lib.check(entry(_ctx(dev).handle, _ptr(frames), _ptr(out), _ptr(affines), F, H, W, C,
@@ -651,23 +663,10 @@ def warp_perspective_u16(frames: torch.Tensor, homographies: torch.Tensor, out: 
     """cv2.warpPerspective(frame, H, (W, H), INTER_LINEAR) for every frame (the warp of
     the homography extension).  frames [F, H, W] or [F, H, W, C] uint16; homographies
     [F, 3, 3] f64 (forward maps, frame -> template, as RANSAC returns them)."""
-    dev = _device_of(frames)
-    if frames.dtype != torch.uint16:
-        raise TypeError(f"frames: expected torch.uint16, got {frames.dtype}")
-    if frames.dim() not in (3, 4):
-        raise ValueError("frames must be [F, H, W] or [F, H, W, C]")
-    _require(frames, "frames", torch.uint16, dev)
-    _require(homographies, "homographies", torch.float64, dev, 3)
+    dev, out = _warp_args(frames, (3, 4), "frames must be [F, H, W] or [F, H, W, C]",
+                          [(homographies, "homographies", torch.float64, (3, 3))], out)
     F, H, W = frames.shape[:3]
     C = 1 if frames.dim() == 3 else frames.shape[3]
-    if homographies.shape != (F, 3, 3):
-        raise ValueError(f"homographies must be [{F}, 3, 3], got {tuple(homographies.shape)}")
-    if out is None:
-        out = torch.empty_like(frames)
-    else:
-        _require(out, "out", torch.uint16, dev)
-        if out.shape != frames.shape:
-            raise ValueError("out must have the shape of frames")
     L = _lib.load()
     _lib.check(L.kcmc_warp_perspective_u16(_ctx(dev).handle, _ptr(frames), _ptr(out), _ptr(homographies), F, H, W, C,
                                            int(bool(inverse_map)), _stream(dev, stream)))
@@ -683,26 +682,11 @@ def warp_field_u16(frames: torch.Tensor, affines: torch.Tensor, field_q: torch.T
 
     frames [F, H, W] uint16 on the device (grayscale only); affines [F, 2, 3] f64.
     """
-    dev = _device_of(frames)
-    if frames.dtype != torch.uint16:
-        raise TypeError(f"frames: expected torch.uint16, got {frames.dtype}")
-    if frames.dim() != 3:
-        raise ValueError("frames must be [F, H, W] (the field warp is grayscale only)")
-    _require(frames, "frames", torch.uint16, dev)
-    _require(affines, "affines", torch.float64, dev, 3)
-    _require(field_q, "field_q", torch.int32, dev, 4)
+    dev, out = _warp_args(frames, (3,), "frames must be [F, H, W] (the field warp is grayscale only)",
+                          [(affines, "affines", torch.float64, (2, 3)),
+                           (field_q, "field_q", torch.int32, ("gy", "gx", 2))], out)
     F, H, W = frames.shape
-    if affines.shape != (F, 2, 3):
-        raise ValueError(f"affines must be [{F}, 2, 3], got {tuple(affines.shape)}")
-    if field_q.shape[0] != F or field_q.shape[3] != 2:
-        raise ValueError(f"field_q must be [{F}, gy, gx, 2], got {tuple(field_q.shape)}")
     gy, gx = int(field_q.shape[1]), int(field_q.shape[2])
-    if out is None:
-        out = torch.empty_like(frames)
-    else:
-        _require(out, "out", torch.uint16, dev)
-        if out.shape != frames.shape:
-            raise ValueError("out must have the shape of frames")
     L = _lib.load()
     _lib.check(L.kcmc_warp_field_u16(_ctx(dev).handle, _ptr(frames), _ptr(out), _ptr(affines), _ptr(field_q), F, H, W,
                                      gy, gx, int(bool(inverse_map)), _stream(dev, stream)))

@@ -80,24 +80,38 @@ CASES = [((1, 1), 2, (3, 120, 264), False), ((2, 3), 2, (2, 61, 75), False), ((5
          ((2, 3), 8, (2, 128, 512), True)]
 
 
+def random_field(grid, amp, shape):
+    """(q, maps) of a case of CASES."""
+    F, H, W = shape
+    rng = np.random.default_rng(grid[0] * 31 + amp)
+    q = rng.integers(-amp * 1024, amp * 1024 + 1, (F,) + grid + (2,)).astype(np.int32)
+    return q, _maps(F, H, W, deg=5.0, seed=amp)  # the last frame: 5 degrees about the centre
+
+
 @pytest.mark.parametrize("grid,amp,shape,dark", CASES)
 def test_random_field_is_the_restatement(dev, grid, amp, shape, dark):
     F, H, W = shape
     base = random_frames(1, H, W, seed=amp * 100 + W, hi=16384 if dark else 65536, n_sat=0 if dark else 7)[0]
     frames = distinct_frames(base, F)
     assert (frames.max() < 16384) if dark else (frames == 65535).any()
-    rng = np.random.default_rng(grid[0] * 31 + amp)
-    q = rng.integers(-amp * 1024, amp * 1024 + 1, (F,) + grid + (2,)).astype(np.int32)
-    M = _maps(F, H, W, deg=5.0, seed=amp)  # the last frame: 5 degrees about the centre
+    q, M = random_field(grid, amp, shape)
     for inv in (False, True):
         np.testing.assert_array_equal(_run(frames, M, q, dev, inverse_map=inv), ref_warp_field(frames, M, q, grid, inv))
 
 
+FAR_SHAPE, FAR_GRID = (2, 120, 264), (3, 3)
+
+
+def far_field():
+    """A field far outside the contract |q| <= 2^20, under identity maps."""
+    return np.random.default_rng(1).integers(-2**31, 2**31 - 1, (FAR_SHAPE[0],) + FAR_GRID + (2,)).astype(np.int32)
+
+
 def test_constant_field_is_a_shift_and_far_fields_stay_in_bounds(dev):
-    F, H, W = 2, 120, 264
+    F, H, W = FAR_SHAPE
     frames = distinct_frames(random_frames(1, H, W, seed=77)[0], F)
     M = np.broadcast_to(np.array([[1.0, 0, 0], [0, 1.0, 0]]), (F, 2, 3)).copy()
-    q = np.zeros((F, 3, 3, 2), np.int32)
+    q = np.zeros((F,) + FAR_GRID + (2,), np.int32)
     q[..., 0], q[..., 1] = -3 * 1024, 2 * 1024  # source = (x - 3, y + 2)
     got = _run(frames, M, q, dev, inverse_map=True)
     np.testing.assert_array_equal(got[:, :H - 2, 3:], frames[:, 2:, :W - 3])
@@ -107,7 +121,7 @@ def test_constant_field_is_a_shift_and_far_fields_stay_in_bounds(dev):
     q[:] = 1 << 20
     assert (_run(frames, M, q, dev, inverse_map=True) == 0).all()
     guard = torch.full((F + 2, H, W), 0xABCD, dtype=torch.uint16, device=dev)
-    q[:] = np.random.default_rng(1).integers(-2**31, 2**31 - 1, q.shape)
+    q[:] = far_field()
     _run(frames, M, q, dev, out=guard[1:F + 1])
     g = guard.cpu().numpy()
     assert (g[0] == 0xABCD).all() and (g[F + 1] == 0xABCD).all()

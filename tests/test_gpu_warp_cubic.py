@@ -124,10 +124,17 @@ def test_forward_maps_are_the_restatement(dev, H, W):
     check(dev, content("random", H, W, len(named), seed=1), named, inverse_map=False)
 
 
+CLAMP_SIZES = [(4, 4), (57, 129), (64, 130), (128, 264)]
+
+
+def clamp_maps(H, W):
+    return [(n, m) for n, m in inverse_maps(H, W) if n[0] == "f" or n.startswith(("rot", "scale", "strip", "ident"))]
+
+
 @pytest.mark.parametrize("kind", ["checker", "bright"])
-@pytest.mark.parametrize("H,W", [(4, 4), (57, 129), (64, 130), (128, 264)])
+@pytest.mark.parametrize("H,W", CLAMP_SIZES)
 def test_clamping_content_is_the_restatement(dev, kind, H, W):
-    named = [(n, m) for n, m in inverse_maps(H, W) if n[0] == "f" or n.startswith(("rot", "scale", "strip", "ident"))]
+    named = clamp_maps(H, W)
     frames = content(kind, H, W, len(named))
     got = check(dev, frames, named, inverse_map=True)
     if kind == "checker" and H > 8:
@@ -137,11 +144,19 @@ def test_clamping_content_is_the_restatement(dev, kind, H, W):
 
 
 # ------------------------------------------------------------------ unaligned slabs
-@pytest.mark.parametrize("H,W", [(57, 129), (64, 136), (65, 130)])
+VIEW_SIZES = [(57, 129), (64, 136), (65, 130)]
+VIEW_OFFSETS = ((1, 1), (0, 1), (1, 0), (1, 8))  # (source, output) elements into their buffers
+
+
+def view_maps(H, W):
+    return [(n, m) for n, m in inverse_maps(H, W) if n in ("identity", "fx7", "fy21", "rot0.02", "rot90", "strip2x.5")]
+
+
+@pytest.mark.parametrize("H,W", VIEW_SIZES)
 def test_views_one_element_into_a_buffer(dev, H, W):
     """A source slab and an output that start 1 element into their buffers: element-wise staging
     (also at W % 8 == 0) and the unpaired store (also at even W)."""
-    named = [(n, m) for n, m in inverse_maps(H, W) if n in ("identity", "fx7", "fy21", "rot0.02", "rot90", "strip2x.5")]
+    named = view_maps(H, W)
     F = len(named)
     frames = content("random", H, W, F, seed=5)
     M = np.stack([m for _, m in named])
@@ -151,7 +166,7 @@ def test_views_one_element_into_a_buffer(dev, H, W):
     sflat[1:1 + n] = torch.from_numpy(frames.reshape(-1)).to(dev)
     oflat = torch.full((n + 9,), SENTINEL, dtype=torch.uint16, device=dev)
     Md = torch.from_numpy(M).to(dev)
-    for s_off, o_off in ((1, 1), (0, 1), (1, 0), (1, 8)):
+    for s_off, o_off in VIEW_OFFSETS:
         oflat.fill_(SENTINEL)
         if s_off == 0:
             src = torch.from_numpy(frames).to(dev)
@@ -167,7 +182,8 @@ def test_views_one_element_into_a_buffer(dev, H, W):
 
 
 # ------------------------------------------------------------------ a seeded sweep
-def test_seeded_sweep_of_random_cases(dev):
+def sweep_cases():
+    """(case, H, W, content kind, inverse_map, map family, maps [3, 2, 3]) of the seeded sweep."""
     rng = np.random.default_rng(20240607)
     for case in range(40):
         H, W = int(rng.integers(1, 201)), int(rng.integers(1, 261))
@@ -190,8 +206,12 @@ def test_seeded_sweep_of_random_cases(dev):
             else:
                 Ms.append(np.array([[rng.uniform(0.9, 1.1), rng.uniform(-0.1, 0.1), rng.uniform(-6, 6)],
                                     [rng.uniform(-0.1, 0.1), rng.uniform(0.9, 1.1), rng.uniform(-6, 6)]]))
-        M = np.stack(Ms)
-        frames = content(kind, H, W, F, seed=case)
+        yield case, H, W, kind, inv, fam, np.stack(Ms)
+
+
+def test_seeded_sweep_of_random_cases(dev):
+    for case, H, W, kind, inv, fam, M in sweep_cases():
+        frames = content(kind, H, W, len(M), seed=case)
         got = run_cubic(dev, frames, M, inv)
         np.testing.assert_array_equal(got, ref_warp_affine_cubic(frames, M, inv),
                                       err_msg=f"case {case}: {H} x {W}, {kind}, family {fam}, inverse_map {inv}")
