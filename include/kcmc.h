@@ -27,6 +27,9 @@
  *   kcmc_stack_sum_u16 / kcmc_frame_stats_u16  <- nothing in the reference (an extension):
  *                             the mean image of the aligned stack and every frame's
  *                             correlation moments with it.
+ *   kcmc_temporal_sums_u16 <- nothing in the reference (an extension): per pixel over time,
+ *                             the sums behind the max projection, the temporal standard
+ *                             deviation and the local correlation image of the aligned stack.
  *   kcmc_shift_search_u16  <- nothing in the reference (an extension): the same moments at
  *                             every integer shift in a window, for the intensity fallback
  *                             of frames without a model.
@@ -512,6 +515,48 @@ int kcmc_stack_sum_u16(kcmc_ctx* ctx, const uint16_t* frames_dev, int n_frames, 
 int kcmc_frame_stats_u16(kcmc_ctx* ctx, const uint16_t* frames_dev, int n_frames, int H, int W,
                          const uint16_t* ref_dev, int y0, int y1, int x0, int x1, long long* out_dev,
                          kcmc_stream_t stream);
+
+/* ------------------------------------------------ q2: summary images (temporal sums)
+ * Build-defined: the reference reports nothing about the aligned stack, and has nothing
+ * like this pass.
+ *
+ * One streaming reduction of frames_dev [n_frames, H, W] u16 per pixel over time, over the
+ * frames f with sel_dev[f] != 0 (sel_dev [n_frames] u8; NULL = every frame; unselected
+ * frames are not loaded) and the pixels p = (y, x) of rows [y0, y1) and columns [x0, x1).
+ * With a_f the value of p in frame f and b_f the value of a partner pixel in the same frame:
+ *
+ *   out_sums_dev [K, H, W] i64, K = 2 + neighbours / 2
+ *     plane 0   sum_f a_f
+ *     plane 1   sum_f a_f^2
+ *     plane 2   sum_f a_f * b_f,  partner (y, x + 1)
+ *     plane 3   sum_f a_f * b_f,  partner (y + 1, x)
+ *     plane 4   sum_f a_f * b_f,  partner (y + 1, x + 1)     neighbours = 8 only
+ *     plane 5   sum_f a_f * b_f,  partner (y + 1, x - 1)     neighbours = 8 only
+ *   out_max_dev [H, W] u16 = max_f a_f
+ *
+ * A pair sum is 0 where the partner lies outside the rectangle (column x1 - 1 never pairs
+ * with column x0 of the next row).  Every output element outside the rectangle is 0; with no
+ * selected frame everything is 0 and the call succeeds.  The other four (eight) neighbours
+ * of a pixel are the same sums read at the partner: sum a(y, x) a(y, x - 1) is plane 2 at
+ * (y, x - 1), and so on.  From these, exactly: the mean and the max projection, the temporal
+ * variance n * plane 1 - plane 0^2, and Pearson's r over time of every pixel with each
+ * neighbour (kcmc_amd.summary).
+ *
+ * Contract (KCMC_EINVAL before any device work otherwise, as for a NULL ctx or pointer):
+ * neighbours 4 or 8; 0 <= y0 < y1 <= H, 0 <= x0 < x1 <= W, H * W < 2^31; out_sums_dev 8-byte
+ * and out_max_dev 4-byte aligned.  out_max_dev is updated in aligned 32-bit words (compare
+ * and swap: the hardware has no 16-bit integer atomics), so when H * W is odd the buffer must
+ * extend 2 bytes past the last pixel; those bytes keep their value.  KCMC_EUNSUPPORTED when
+ * tiles times frame chunks reach 2^31.  Any n_frames (plane 1 and the pair planes stay below
+ * 2^31 * 65535^2 < 2^63), any W and alignment of frames_dev: the 16-byte path needs
+ * W % 8 == 0 and a 16-byte aligned frames_dev, everything else is read element by element.
+ *
+ * Exact: every sum is a 64-bit integer (the results do not depend on the order in which
+ * workgroups finish).  Asynchronous on `stream`, capturable, no allocation; zeroes its own
+ * outputs first. */
+int kcmc_temporal_sums_u16(kcmc_ctx* ctx, const uint16_t* frames_dev, int n_frames, int H, int W,
+                           const uint8_t* sel_dev, int y0, int y1, int x0, int x1, int neighbours,
+                           long long* out_sums_dev, uint16_t* out_max_dev, kcmc_stream_t stream);
 
 /* ------------------------------------- s1: exact shift search (intensity fallback)
  * Build-defined: the reference never registers a frame RANSAC gave no model (it

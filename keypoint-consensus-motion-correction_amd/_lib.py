@@ -66,6 +66,7 @@ EXPORTED_SYMBOLS = (
     "kcmc_tile_gradient_sums_u16",
     "kcmc_bidi_phase_sums_u16",
     "kcmc_shift_rows_u16",
+    "kcmc_temporal_sums_u16",
 )
 
 KCMC_MODEL_EUCLIDEAN = 0
@@ -142,6 +143,7 @@ _SIGNATURES = {
     "kcmc_tile_gradient_sums_u16": ([P, P, I, I, I, P, I, P, P, I, P, I, P, P], I),
     "kcmc_bidi_phase_sums_u16": ([P, P, I, I, I, P, I, I, P, P], I),
     "kcmc_shift_rows_u16": ([P, P, P, I, I, I, I, I, P], I),
+    "kcmc_temporal_sums_u16": ([P, P, I, I, I, P, I, I, I, I, I, P, P, P], I),
 }
 
 

@@ -1,6 +1,6 @@
 // Rows of uint16 pixels as 16-byte vectors of eight, and what the exact-integer passes over
-// a uint16 stack share around them: quality.hip (q1), shift_search.hip (s1), refine.hip (g1),
-// refine_tiles.hip (g2).
+// a uint16 stack share around them: quality.hip (q1), temporal_sums.hip (q2), shift_search.hip
+// (s1), refine.hip (g1), refine_tiles.hip (g2).
 #pragma once
 
 #include "kcmc_internal.h"

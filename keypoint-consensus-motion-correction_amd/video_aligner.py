@@ -40,6 +40,7 @@ from . import quality as _q
 from . import refine as _rf
 from . import refine_field as _rff
 from . import stages
+from . import summary as _sm
 from .affines import AlignmentError
 
 
@@ -156,6 +157,17 @@ class VideoAligner:
     # detection and keypoints are reused; only the template is detected again.
     TEMPLATE_REFINE_ITERS = 0
     TEMPLATE_REFINE_TOP_FRAC = 0.5
+    # New (opt-in, kcmc_amd.summary; build-defined, the reference reports nothing about the
+    # aligned stack): the summary images of the last pass's aligned stack, over all its frames
+    # and the region valid in every frame (summary_region, quality.valid_region of the final
+    # maps) -- summary_mean_image, max_image (the max projection), std_image (the temporal
+    # standard deviation), correlation_image (each pixel's mean correlation over time with its
+    # SUMMARY_NEIGHBOURS = 4 or 8 neighbours) and crispness (the norm of the mean image's
+    # gradient), from one more read of the stack (csrc/temporal_sums.hip).  Needs no
+    # QUALITY_METRICS and leaves its results alone.  Grayscale stacks, 2 x 3 models, not with
+    # PIECEWISE_GRID / REFINE_GRID.
+    SUMMARY_IMAGES = False
+    SUMMARY_NEIGHBOURS = 8
     # New (opt-in, kcmc_amd.piecewise; build-defined, the reference has no such mode):
     # piecewise-rigid correction.  (gy, gx), each in [1, 16]: after the global RANSAC every sample
     # frame fits one rigid model per grid cell from the consensus points in the cell's window
@@ -253,6 +265,7 @@ class VideoAligner:
         self._des_template = None
         self._logged_one_device = False
         self._reset_quality()
+        self._reset_summary()
         self._reset_piecewise()
         self._reset_fallback()
         self._reset_refine()
@@ -617,6 +630,54 @@ class VideoAligner:
             res = hot()
         return res
 
+    # ------------------------------------------------- summary images of the aligned stack
+    def _reset_summary(self) -> None:
+        self.summary_region = None
+        self.summary_mean_image = None
+        self.max_image = None
+        self.std_image = None
+        self.correlation_image = None
+        self.crispness = None
+
+    def _summary_on(self, images=None) -> bool:
+        """Whether the summary images are made, after the checks that must fail before any work
+        (``images``: only its number of dimensions is read, when it has one)."""
+        if not self.SUMMARY_IMAGES:
+            return False
+        try:
+            _sm.check_neighbours(self.SUMMARY_NEIGHBOURS)
+        except ValueError:
+            raise ValueError(f"SUMMARY_NEIGHBOURS must be 4 or 8, got {self.SUMMARY_NEIGHBOURS!r}") from None
+        if self.RANSAC_MODEL == "projective":
+            raise NotImplementedError("SUMMARY_IMAGES does not support RANSAC_MODEL = 'projective' (a homography's "
+                                      "displacement is not bounded by its corners)")
+        if self.PIECEWISE_GRID is not None or self.REFINE_GRID is not None:
+            raise NotImplementedError("SUMMARY_IMAGES does not run together with PIECEWISE_GRID / REFINE_GRID (the "
+                                      "valid region of a field warp is not defined yet)")
+        if getattr(images, "ndim", 3) != 3:
+            raise NotImplementedError("SUMMARY_IMAGES supports grayscale stacks [F, H, W] only")
+        return True
+
+    def _summarize(self, res, n_images: int) -> None:
+        """The summary images of the final pass (res: a SlabResult or SplitResult, frames still on
+        their devices and unpatched), over all frames."""
+        parts = _in.parts_of(res)
+        if parts[0].dim() != 3:
+            raise NotImplementedError("SUMMARY_IMAGES supports grayscale stacks [F, H, W] only")
+        H, W = parts[0].shape[1:]
+        region = _q.valid_region(np.asarray(res.affines)[:n_images], H, W,
+                                 taps=4 if self._interpolation_on() == "cubic" else 2)
+        n, planes, top = _sm.temporal_sums(parts, region, None, int(self.SUMMARY_NEIGHBOURS))
+        planes = planes.cpu().numpy()
+        self.summary_region = region
+        self.summary_mean_image = _sm.mean_image(planes, n, region)
+        self.max_image = top.cpu().numpy()
+        self.std_image = _sm.std_image(planes, n, region)
+        self.correlation_image = _sm.correlation_image(planes, n, region)
+        self.crispness = _sm.crispness(self.summary_mean_image, region)
+        self.logger.info(f"summary images over {n} frames, rows [{region[0]}, {region[1]}), columns "
+                         f"[{region[2]}, {region[3]}): crispness {self.crispness:.3f}")
+
     # ------------------------------------------------------------- public API
     def _begin(self, images, refine_supported: bool) -> None:
         """What align_images and align_keypoints open with: the results of the switches reset and
@@ -627,6 +688,8 @@ class VideoAligner:
         self._bidi_on(images)
         self._reset_quality()
         self._quality_on(refine_supported)
+        self._reset_summary()
+        self._summary_on(images)
         self._reset_piecewise()
         self._piecewise_on(images)
         self._reset_fallback()
@@ -771,6 +834,8 @@ class VideoAligner:
         hot = self._with_refine(self._with_fallback(hot, slabs, n_images, rate), slabs, n_images, rate)
         # the metrics read the aligned slabs where they are, before they are gathered
         res = self._run_passes(hot, slabs, n_images, rate, detect_template)
+        if self._summary_on():
+            self._summarize(res, n_images)
         self.interpolated_idxs = res.interpolated
         self.logger.info(f"aligned frames in: {round(time.time() - t_start)} s")
         self._take_piecewise(res)
