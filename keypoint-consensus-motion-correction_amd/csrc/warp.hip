@@ -12,42 +12,37 @@
 // operation by operation.
 //
 // Layout: frames [F, H, W, C] u16 contiguous in HBM, processed in 128 x 56 output
-// tiles.  Because the fixed-point source coordinate is separable (X = X0[y] + adelta[x])
-// and monotone, the exact source bounding box of a tile follows from its corner values;
-// the box is staged into LDS with coalesced 16-byte loads (zero outside the image,
-// which is exactly BORDER_CONSTANT) and every output pixel gathers its four taps from
-// LDS with aligned 16-bit reads.  A wave makes one 128-pixel output row at a time
-// (lane l: pixels 2l, 2l+1, one 4-byte store), so its tap reads cover consecutive LDS
-// words without bank conflicts and its row-level state is wave-uniform.  Tiles whose box exceeds the staging budget (strong
-// zoom-out or rotation) gather from global memory instead; tiles whose box misses the
-// image store zeros.
+// tiles on the skeleton of warp_tile.h (plan struct, tile decode, box staging, column
+// deltas, row origins).  Because the fixed-point source coordinate is separable
+// (X = X0[y] + adelta[x]) and monotone, the exact source bounding box of a tile follows
+// from its corner values (affine_box); the box is staged into LDS with coalesced 16-byte
+// loads (zero outside the image, which is exactly BORDER_CONSTANT) and every output pixel
+// gathers its four taps from LDS with aligned 16-bit reads.  A wave makes one 128-pixel
+// output row at a time (lane l: pixels 2l, 2l+1, one 4-byte store), so its tap reads cover
+// consecutive LDS words without bank conflicts and its row-level state is wave-uniform.
+// Tiles whose box exceeds the staging budget (strong zoom-out or rotation) gather from
+// global memory instead; tiles whose box misses the image store zeros.
 //
-// One-channel frames with W % 8 == 0 and a box that fits a fixed 144-pixel LDS pitch (the
-// near-identity maps of motion correction) take a leaner form of the same path (mode 3,
-// fast_rows): the box staged by range-checked buffer loads at a constant row stride per
-// thread (FastStage: the descriptor's range check is the zero border, one add per pass),
-// scalar per-row origins from a per-frame table, immediate-offset taps, buffer
-// stores, and a per-tile choice of blend from the staged values (exact integer blend with
-// no range check when every value is < 16384; with a few bright values the integer blend
-// and OpenCV's float blend only for rows with a sum near a rounding tie; the float blend on
-// packed fp32 for bright boxes).
+// Frames with W % 8 == 0 and a box that fits a fixed 144-pixel LDS pitch (the near-identity
+// maps of motion correction) take a leaner form of the same path (mode 3, fast_rows): one
+// plane per channel at the fixed pitch -- one channel staged by range-checked buffer loads
+// at a constant row stride per thread (Fast<Cfg, 1>: the descriptor's range check is the
+// zero border, one add per pass), three or four de-interleaved while they land --, scalar
+// per-row origins from a per-frame table, immediate-offset taps, buffer stores, and a
+// per-tile choice of blend from the staged values (exact integer blend with no range check
+// when every value is < 16384; with a few bright values the integer blend and OpenCV's
+// float blend only for rows with a sum near a rounding tie; the float blend on packed fp32
+// for bright boxes).
 //
 // Two launches: warp_plan_kernel (one thread per tile) inverts the map in fp64 and
 // derives each tile's source box and the frame's row-origin table, so that the tile
 // kernel starts with scalar loads of its plan and issues its staging loads immediately; warp_affine_u16_kernel then makes
 // one tile per workgroup, latency hidden by the other resident workgroups (a persistent
 // double-buffered variant measured 25% slower).
-#include <climits>
-
-#include "kcmc_internal.h"
-#include "warp_common.h"  // cv_round, sat_u16, sat_s16, invert_affine, load_map, blend_int, bilinear_px
+#include "warp_tile.h"  // the tile skeleton; warp_common.h: cv_round, load_map, blend_int, bilinear_px
 
 namespace kcmc {
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kTileW = 128;     // output columns per tile (64 lanes x 2 pixels)
-constexpr int kMaxPitch = 256;  // staged row length limit (32 x 16-byte chunks)
 
 template <int TILE_H, int LDS_ELEMS, int ROW_PASSES>
 struct WarpCfg {
@@ -55,164 +50,100 @@ struct WarpCfg {
   static constexpr int kLdsElems = LDS_ELEMS;    // uint16 staging budget per box
   static constexpr int kRowPasses = ROW_PASSES;  // staging passes of 8 rows x 32 chunks
 };
-using BlockCfg = WarpCfg<56, 10240, 9>;  // 20 KB box, box rows <= 72 (7 workgroups per CU)
-// Frame heights that are a multiple of 64 but not of 56 (512: config 3) lose 9 % of their
-// tiles to a partial last tile row at 56 rows; 64-row tiles with the same 20 KB box budget
-// cover them exactly (the fast path's 71 staged rows still hold a 64-row tile rotated by up
-// to ~2.5 deg; larger rotations take the general staged path or the direct gather).
-using Block64Cfg = WarpCfg<64, 10240, 9>;
-
-// one-channel tile height for a frame height (round 3)
-inline bool use_tile64(int H) { return H % 64 == 0 && H % 56 != 0; }
+using BlockCfg = WarpCfg<56, kLdsElems, kRowPasses>;  // 20 KB box, box rows <= 72 (7 workgroups per CU)
+// use_tile64 frames: 64-row tiles with the same 20 KB box budget cover them exactly (the
+// fast path's 71 staged rows still hold a 64-row tile rotated by up to ~2.5 deg; larger
+// rotations take the general staged path or the direct gather).
+using Block64Cfg = WarpCfg<64, kLdsElems, kRowPasses>;
 // Multi-channel frames (RGB / RGBA, config 4): 3-4x the bytes per box pixel, so shorter
 // tiles keep the interleaved box in a 32 KB LDS budget (box rows <= 32).
 using ChanCfg = WarpCfg<24, 16384, 4>;
 
 template <int C>
 struct CfgFor {
-  using type = BlockCfg;
-};
-template <>
-struct CfgFor<3> {
-  using type = ChanCfg;
-};
-template <>
-struct CfgFor<4> {
-  using type = ChanCfg;
+  using type = std::conditional_t<C == 1, BlockCfg, ChanCfg>;
 };
 
-// Fast staged path (mode 3; one channel, W % 8 == 0, the near-identity maps of motion
-// correction): the box is staged at a fixed LDS pitch, so the lower tap row is an
-// immediate offset of the upper one, and the per-row source origins come from a per-frame
-// table through scalar loads.  Boxes wider than kFastPitch or taller than kFastRows take
-// the general staged path (mode 0).
-constexpr int kFastPitch = 144;  // pixels: 128-px tile + up to ~8 deg / 6 % zoom
-constexpr int kFastChunks = kFastPitch / 8;  // 16-byte chunks per staged row
-template <class Cfg>
-struct Fast {
-  static constexpr int kRows = (Cfg::kLdsElems - 8) / kFastPitch;  // the last 16 bytes: per-wave flags
-  static constexpr int kFlagWord = Cfg::kLdsElems / 2 - 4;          // uint32 index of the flags
-};
-
-struct Box {
-  int mode;   // 0: staged in LDS, 1: every tap outside the image (zeros), 2: direct gather
-  int ax0;    // first staged column (multiple of 8)
-  int sy0;    // first staged row
-  int pitch;  // staged row length in pixels (multiple of 8)
-  int rows;
-};
+// The plan of a tile whose taps lie in source columns sx0..sx1 and rows sy0..sy1 (classify_box
+// with this file's budgets: `budget` elements for the C-channel box under Cfg).  small: the box
+// is clear of OpenCV's saturate_cast<short> on coordinates; stage_ok: it may be staged.
+template <class Cfg, int C>
+__device__ __forceinline__ TilePlan box_plan(long long sx0, long long sx1, long long sy0, long long sy1, int H, int W,
+                                             bool small, bool stage_ok, int budget) {
+  const long long ax0 = (sx0 >> 3) << 3;
+  const long long pitch = ((sx1 - ax0 + 1) + 7) & ~7ll;
+  const long long rows = sy1 - sy0 + 1;
+  int mode = 2;
+  if (small && (sx1 < 0 || sx0 > W - 1 || sy1 < 0 || sy0 > H - 1))
+    mode = 1;
+  else if (small && stage_ok && pitch <= kMaxPitch && rows <= 8 * Cfg::kRowPasses && pitch * rows * C <= budget)
+    mode = 0;
+  return TilePlan{mode, (int)ax0, (int)sy0, (int)pitch | ((int)rows << 16)};
+}
 
 // The source box of the tile's valid pixels.  adelta[x] = cvRound(M0*x*1024) and
 // X0[y] = cvRound((M1*y + M2)*1024) + 16 are monotone in x and y (monotone products,
 // sums and rounding), so their extremes sit at the tile's first/last valid column/row
-// and sx = (X0[y] + adelta[x]) >> 10 spans [min, max] exactly; the second tap adds 1.
+// (affine_box) and sx = (X0[y] + adelta[x]) >> 10 spans [min, max] exactly; the second tap adds 1.
 template <class Cfg, int C>
-__device__ __forceinline__ Box source_box(const double* M, int xb, int yb, int H, int W) {
-  const int xl = min(xb + kTileW, W) - 1, yl = min(yb + Cfg::kTileH, H) - 1;
-  const long long a0 = cv_round(M[0] * xb * 1024), a1 = cv_round(M[0] * xl * 1024);
-  const long long b0 = cv_round(M[3] * xb * 1024), b1 = cv_round(M[3] * xl * 1024);
-  const long long x0 = cv_round((M[1] * yb + M[2]) * 1024) + 16, x1 = cv_round((M[1] * yl + M[2]) * 1024) + 16;
-  const long long y0 = cv_round((M[4] * yb + M[5]) * 1024) + 16, y1 = cv_round((M[4] * yl + M[5]) * 1024) + 16;
-  const long long sx0 = (min(x0, x1) + min(a0, a1)) >> 10, sx1 = ((max(x0, x1) + max(a0, a1)) >> 10) + 1;
-  const long long sy0 = (min(y0, y1) + min(b0, b1)) >> 10, sy1 = ((max(y0, y1) + max(b0, b1)) >> 10) + 1;
-  Box b;
+__device__ __forceinline__ TilePlan source_box(const PlanTile& p, int H, int W) {
+  const Box1024 b = affine_box(p.M, p.xb, p.yb, p.xl, p.yl);
+  const long long sx0 = b.x0 >> 10, sx1 = (b.x1 >> 10) + 1, sy0 = b.y0 >> 10, sy1 = (b.y1 >> 10) + 1;
   const long long lim = 30000;  // keep clear of OpenCV's saturate_cast<short> on coordinates
   const bool small = sx0 > -lim && sx1 < lim && sy0 > -lim && sy1 < lim;
-  const long long ax0 = (sx0 >> 3) << 3;
-  const long long pitch = ((sx1 - ax0 + 1) + 7) & ~7ll;
-  const long long rows = sy1 - sy0 + 1;
-  b.mode = 2;
-  if (small && (sx1 < 0 || sx0 > W - 1 || sy1 < 0 || sy0 > H - 1))
-    b.mode = 1;
-  else if (small && pitch <= kMaxPitch && rows <= 8 * Cfg::kRowPasses && pitch * rows * C <= Cfg::kLdsElems)
-    b.mode = 0;
-  b.ax0 = (int)ax0;
-  b.sy0 = (int)sy0;
-  b.pitch = (int)pitch;
-  b.rows = (int)rows;
-  return b;
+  return box_plan<Cfg, C>(sx0, sx1, sy0, sy1, H, W, small, true, Cfg::kLdsElems);
 }
 
-// Staging of a box.  With C == 1 and W % 8 == 0 every 16-byte chunk is entirely inside
-// or entirely outside the image (zeros).  Thread = (chunk c = tid & 31, row r = tid>>5 + 8k).
-template <class Cfg>
-__device__ __forceinline__ void stage_issue(const uint16_t* __restrict__ S, const Box& box, int H, int W, int tid,
-                                            uint4 (&chunk)[Cfg::kRowPasses]) {
-  const int cpr = box.pitch >> 3;
-  const int sc = tid & 31, sr = tid >> 5;
-  const int gx = box.ax0 + 8 * sc;
-  const bool col_ok = sc < cpr && gx >= 0 && gx < W;
-#pragma unroll
-  for (int k = 0; k < Cfg::kRowPasses; ++k) {
-    const int r = sr + 8 * k;
-    const int gy = box.sy0 + r;
-    chunk[k] = make_uint4(0u, 0u, 0u, 0u);
-    if (r < box.rows && col_ok && (unsigned)gy < (unsigned)H)
-      chunk[k] = *reinterpret_cast<const uint4*>(S + (size_t)gy * W + gx);
-  }
-}
-
-template <class Cfg>
-__device__ __forceinline__ void stage_land(uint16_t* stile, const Box& box, int tid,
-                                           const uint4 (&chunk)[Cfg::kRowPasses]) {
-  const int cpr = box.pitch >> 3;
-  const int sc = tid & 31, sr = tid >> 5;
-#pragma unroll
-  for (int k = 0; k < Cfg::kRowPasses; ++k) {
-    const int r = sr + 8 * k;
-    if (r < box.rows && sc < cpr) *reinterpret_cast<uint4*>(&stile[r * box.pitch + 8 * sc]) = chunk[k];
-  }
-}
-
-// Staging of a C-channel box with 16-byte chunks of the interleaved rows (W % 8 == 0:
-// ax0 and W are multiples of 8 pixels, so a chunk is entirely inside or outside the
-// image row and zero-filling whole chunks is exactly BORDER_CONSTANT).  Chunk
-// q = tid + kThreads * k of the box; every load of a thread is issued before any lands
+// Generic staging of a mode-0 box, issue before the kernel's own work and land after.  One
+// channel: stage_load / stage_commit (with W % 8 == 0 every 16-byte chunk is entirely inside
+// or entirely outside the image; element-wise otherwise).  C channels with W % 8 == 0: 16-byte
+// chunks of the interleaved rows (ax0 and W are multiples of 8 pixels, so a chunk is entirely
+// inside or outside the image row and zero-filling whole chunks is exactly BORDER_CONSTANT),
+// chunk q = tid + kThreads * k of the box; every load of a thread is issued before any lands
 // (a load-then-store loop waits for each load in turn: the 4K RGB warp took 14.6 ms per
 // 625 frames that way, 11.8 ms with the loads in flight together).
 template <class Cfg, int C>
-struct VecC {
-  static constexpr int kPasses = (Cfg::kLdsElems / 8 + kThreads - 1) / kThreads;
+struct BoxLoads {
+  static constexpr int kPasses = C == 1 ? Cfg::kRowPasses : (Cfg::kLdsElems / 8 + kThreads - 1) / kThreads;
+  uint4 chunk[kPasses];
 };
 
 template <class Cfg, int C>
-__device__ __forceinline__ void stage_vec_c_issue(const uint16_t* __restrict__ S, const Box& box, int H, int W,
-                                                  int tid, uint4 (&chunk)[VecC<Cfg, C>::kPasses]) {
-  const int cpr = box.pitch * C / 8;
-  const int total = box.rows * cpr;
-  const int rowe = W * C;
+__device__ __forceinline__ void box_issue(const uint16_t* __restrict__ S, const TilePlan& tp, int H, int W,
+                                          BoxLoads<Cfg, C>& l) {
+  if (tp.mode != 0 || (W & 7) != 0) return;
+  if constexpr (C == 1) {
+    stage_load(S, tp, H, W, true, l.chunk);
+  } else {
+    const int tid = threadIdx.x, cpr = tp.pitch() * C / 8, total = tp.rows() * cpr, rowe = W * C;
 #pragma unroll
-  for (int k = 0; k < VecC<Cfg, C>::kPasses; ++k) {
-    const int q = tid + kThreads * k;
-    const int r = q / cpr, cc = q - r * cpr;
-    const int gy = box.sy0 + r;
-    const int e = box.ax0 * C + 8 * cc;
-    chunk[k] = make_uint4(0u, 0u, 0u, 0u);
-    if (q < total && (unsigned)gy < (unsigned)H && e >= 0 && e < rowe)
-      chunk[k] = *reinterpret_cast<const uint4*>(S + (size_t)gy * rowe + e);
+    for (int k = 0; k < BoxLoads<Cfg, C>::kPasses; ++k) {
+      const int q = tid + kThreads * k;
+      const int r = q / cpr, cc = q - r * cpr;
+      const int gy = tp.sy0 + r;
+      const int e = tp.ax0 * C + 8 * cc;
+      l.chunk[k] = make_uint4(0u, 0u, 0u, 0u);
+      if (q < total && (unsigned)gy < (unsigned)H && e >= 0 && e < rowe)
+        l.chunk[k] = *reinterpret_cast<const uint4*>(S + (size_t)gy * rowe + e);
+    }
   }
 }
 
 template <class Cfg, int C>
-__device__ __forceinline__ void stage_vec_c_land(uint16_t* stile, const Box& box, int tid,
-                                                 const uint4 (&chunk)[VecC<Cfg, C>::kPasses]) {
-  const int total = box.rows * (box.pitch * C / 8);
+__device__ __forceinline__ void box_land(uint16_t* stile, const uint16_t* __restrict__ S, const TilePlan& tp, int H,
+                                         int W, const BoxLoads<Cfg, C>& l) {
+  if (tp.mode != 0) return;
+  if constexpr (C == 1) {
+    stage_commit(stile, S, tp, H, W, (W & 7) == 0, l.chunk);
+  } else if ((W & 7) == 0) {
+    const int tid = threadIdx.x, total = tp.rows() * (tp.pitch() * C / 8);
 #pragma unroll
-  for (int k = 0; k < VecC<Cfg, C>::kPasses; ++k) {
-    const int q = tid + kThreads * k;
-    if (q < total) reinterpret_cast<uint4*>(stile)[q] = chunk[k];
-  }
-}
-
-// Element-wise staging (W % 8 != 0).
-template <int C>
-__device__ __forceinline__ void stage_scalar(const uint16_t* __restrict__ S, uint16_t* stile, const Box& box, int H,
-                                             int W, int tid) {
-  for (int q = tid; q < box.rows * box.pitch * C; q += kThreads) {
-    const int r = q / (box.pitch * C), e = q - r * box.pitch * C;
-    const int gy = box.sy0 + r, gx = box.ax0 + e / C, k = e % C;
-    stile[q] = ((unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W) ? S[((size_t)gy * W + gx) * C + k]
-                                                                          : (uint16_t)0;
+    for (int k = 0; k < BoxLoads<Cfg, C>::kPasses; ++k) {
+      const int q = tid + kThreads * k;
+      if (q < total) reinterpret_cast<uint4*>(stile)[q] = l.chunk[k];
+    }
+  } else {
+    stage_elements<C>(stile, S, tp, H, W);
   }
 }
 
@@ -246,84 +177,173 @@ __device__ __forceinline__ uint32_t tap(const uint16_t* stile, int i) { return s
 // built library for that pattern).
 __device__ __forceinline__ uint32_t bfe_11_5(uint32_t v) { return __builtin_amdgcn_ubfe(v, 11, 5); }
 
+// The wave's count of lanes whose chunk (its dwords OR-ed into v) holds a value >= 16384.
+__device__ __forceinline__ uint32_t bright_lanes(uint32_t v) {
+  return __builtin_popcountll(__builtin_amdgcn_ballot_w64((v & 0xc000c000u) != 0));
+}
+__device__ __forceinline__ uint32_t bright_chunks(const uint4& v) { return bright_lanes(v.x | v.y | v.z | v.w); }
 
-// Fast-path staging.  Thread tid owns chunk column c = tid % kFastChunks and the box rows
-// r0 + kStep k (r0 = tid / kFastChunks, kStep = 14: 252 of the 256 threads), so the row-major
-// LDS slot of pass k is 16 tid + an immediate, and the source byte offset of pass k is the
-// thread's first offset plus k times a wave-uniform stride: one add per pass.  The loads are
-// raw buffer loads through one descriptor per tile, base = the frame, num_records = the
-// bytes of the frame down to the box's last row; the hardware range check of voffset then
-// returns the zeros of BORDER_CONSTANT for rows above the frame (the 32-bit offset wraps
-// beyond 2^31 > num_records: H, W < 2^15, |row| <= 30000), for rows below it and for rows
-// below the box (not fetched), and a row never reads the neighbouring frame.  The column
-// test is paid once: a thread whose chunk is outside the box's pitch or the frame's columns
-// (or one of the 4 spare threads) starts at offset 2^31, out of range for every pass.  So
-// the load passes hold no exec-mask branch, no zero-initialised registers and no 64-bit
+// Fast staged path (mode 3; W % 8 == 0, the near-identity maps of motion correction): the
+// box is staged as C channel planes at a fixed LDS pitch, so the lower tap row and the other
+// planes are immediate offsets of the upper tap, and the per-row source origins come from a
+// per-frame table through scalar loads.  Boxes wider than kFastPitch or taller than kRows
+// take the general staged path (mode 0).
+// pixels: 128-px tile + up to ~8 deg / 6 % zoom (192: fewer bank conflicts, same time)
+constexpr int kFastPitch = 144;
+constexpr int kFastChunks = kFastPitch / 8;  // 16-byte chunks (8-pixel groups) per staged row
+template <class Cfg, int C>
+struct FastPlanes {
+  static constexpr int kRows = (Cfg::kLdsElems - 8) / (C * kFastPitch);  // the last 16 bytes: per-wave flags
+  static constexpr int kPlane = kRows * kFastPitch;                      // elements per channel plane
+  static constexpr int kFlagWord = Cfg::kLdsElems / 2 - 4;               // uint32 index of the flags
+  static_assert(C * kPlane <= 2 * kFlagWord, "planes overlap the flag words");
+};
+
+// word i of plane k of an 8-pixel group: elements C (2i) + k and C (2i + 1) + k of the
+// interleaved group (dwords d[e / 2], halves e % 2), as one v_perm_b32
+template <int C, int K, int I>
+__device__ __forceinline__ uint32_t plane_word(const uint32_t (&d)[4 * C]) {
+  constexpr int e0 = C * 2 * I + K, e1 = C * (2 * I + 1) + K;
+  constexpr uint32_t sel = ((e0 & 1) ? 0x0302u : 0x0100u) | ((e1 & 1) ? 0x07060000u : 0x05040000u);
+  return __builtin_amdgcn_perm(d[e1 / 2], d[e0 / 2], sel);
+}
+
+template <int C, int K>
+__device__ __forceinline__ uint4 plane_piece(const uint32_t (&d)[4 * C]) {
+  return make_uint4(plane_word<C, K, 0>(d), plane_word<C, K, 1>(d), plane_word<C, K, 2>(d), plane_word<C, K, 3>(d));
+}
+
+// Fast-path staging for C = 3 / 4 (round 4): issue() loads, land() stores and returns the wave's
+// count of bright (>= 16384) groups.  The interleaved box is de-interleaved while it lands:
+// each thread loads one 8-pixel group of a box row (C 16-byte chunks, 16-byte aligned because
+// ax0 and W are multiples of 8) and writes C planar 16-byte pieces (v_perm_b32 pairs), one per
+// channel plane, at the fixed pitch.  A pixel's taps then sit at the same offset in every plane
+// (immediate offsets), so the coordinate work of a pixel is shared by its C channels, and each
+// lane's C output dwords (pixels 2l, 2l+1) leave in ONE 12- / 16-byte store: a wave's store
+// covers 768 / 1024 contiguous bytes of the row.  The general multi-channel path (mode 0) reads
+// interleaved taps with per-channel addressing and stores C separate dwords per lane at a
+// 12-byte lane stride (round 3: 148 VALU, 49 SALU, 25 LDS instructions per wave row at c4).
+template <class Cfg, int C>
+struct Fast : FastPlanes<Cfg, C> {
+  static constexpr int kPasses = (Fast::kRows * kFastChunks + kThreads - 1) / kThreads;
+  struct Loads {
+    uint4 g[kPasses][C];
+  };
+
+  static __device__ __forceinline__ void issue(const uint16_t* __restrict__ S, const TilePlan& tp, int H, int W,
+                                               int tid, Loads& l) {
+    const int gpr = tp.pitch() >> 3, rows = tp.rows();
+#pragma unroll
+    for (int k = 0; k < kPasses; ++k) {
+      const int q = tid + kThreads * k;
+      const int r = q / kFastChunks, c = q - r * kFastChunks;
+      const int gy = tp.sy0 + r, gx = tp.ax0 + 8 * c;
+      const bool ok = r < rows && c < gpr && (unsigned)gx < (unsigned)W && (unsigned)gy < (unsigned)H;
+#pragma unroll
+      for (int j = 0; j < C; ++j) l.g[k][j] = make_uint4(0u, 0u, 0u, 0u);
+      if (ok) {
+        const uint4* src = reinterpret_cast<const uint4*>(S + ((size_t)gy * W + gx) * C);
+#pragma unroll
+        for (int j = 0; j < C; ++j) l.g[k][j] = src[j];
+      }
+    }
+  }
+
+  static __device__ __forceinline__ uint32_t land(uint16_t* stile, const TilePlan& tp, int tid, const Loads& l) {
+    const int gpr = tp.pitch() >> 3, rows = tp.rows();
+    uint32_t nb = 0;
+#pragma unroll
+    for (int k = 0; k < kPasses; ++k) {
+      const int q = tid + kThreads * k;
+      const int r = q / kFastChunks, c = q - r * kFastChunks;
+      uint32_t d[4 * C], any = 0;  // the group's 8 C elements, two per dword
+#pragma unroll
+      for (int j = 0; j < C; ++j) {
+        d[4 * j] = l.g[k][j].x;
+        d[4 * j + 1] = l.g[k][j].y;
+        d[4 * j + 2] = l.g[k][j].z;
+        d[4 * j + 3] = l.g[k][j].w;
+        any |= l.g[k][j].x | l.g[k][j].y | l.g[k][j].z | l.g[k][j].w;
+      }
+      nb += bright_lanes(any);
+      if (r < rows && c < gpr) {
+        uint4* dst = reinterpret_cast<uint4*>(stile + r * kFastPitch + 8 * c);
+        dst[0] = plane_piece<C, 0>(d);
+        dst[Fast::kPlane / 8] = plane_piece<C, 1>(d);
+        dst[2 * Fast::kPlane / 8] = plane_piece<C, 2>(d);
+        if constexpr (C == 4) dst[3 * Fast::kPlane / 8] = plane_piece<C, 3>(d);
+      }
+    }
+    return nb;
+  }
+};
+
+// Fast-path staging for one channel.  Thread tid owns chunk column c = tid % kFastChunks and
+// the box rows r0 + kStep k (r0 = tid / kFastChunks, kStep = 14: 252 of the 256 threads), so
+// the row-major LDS slot of pass k is 16 tid + an immediate, and the source byte offset of
+// pass k is the thread's first offset plus k times a wave-uniform stride: one add per pass.
+// The loads are raw buffer loads through one descriptor per tile, base = the frame,
+// num_records = the bytes of the frame down to the box's last row; the hardware range check
+// of voffset then returns the zeros of BORDER_CONSTANT for rows above the frame (the 32-bit
+// offset wraps beyond 2^31 > num_records: H, W < 2^15, |row| <= 30000), for rows below it and
+// for rows below the box (not fetched), and a row never reads the neighbouring frame.  The
+// column test is paid once: a thread whose chunk is outside the box's pitch or the frame's
+// columns (or one of the 4 spare threads) starts at offset 2^31, out of range for every pass.
+// So the load passes hold no exec-mask branch, no zero-initialised registers and no 64-bit
 // address arithmetic.  kPasses whole passes cover rows 0 .. kPasses * kStep - 1 (69); a box
 // with more rows (the 71st, rare) stages the rest in a tail pass behind a wave-uniform branch.
 template <class Cfg>
-struct FastStage {
-  static constexpr int kStep = kThreads / kFastChunks;        // box rows per pass (14)
-  static constexpr int kUsed = kStep * kFastChunks;           // staging threads (252)
-  static constexpr int kPasses = Fast<Cfg>::kRows / kStep;    // whole passes (5)
-  static constexpr int kTailRows = Fast<Cfg>::kRows - kPasses * kStep;  // rows of the tail pass (1)
+struct Fast<Cfg, 1> : FastPlanes<Cfg, 1> {
+  static constexpr int kStep = kThreads / kFastChunks;               // box rows per pass (14)
+  static constexpr int kUsed = kStep * kFastChunks;                  // staging threads (252)
+  static constexpr int kPasses = Fast::kRows / kStep;                // whole passes (5)
+  static constexpr int kTailRows = Fast::kRows - kPasses * kStep;    // rows of the tail pass (1)
   static_assert(kTailRows < kStep && kTailRows * kFastChunks <= kThreads, "one tail pass");
-};
+  struct Loads {
+    uint4 chunk[kPasses];
+    __amdgpu_buffer_rsrc_t rsrc;
+    uint32_t voff;  // byte offset of the thread's chunk in box row r0 (2^31: never in range)
+    uint32_t step;  // bytes of kStep frame rows (wave-uniform)
+    __device__ __forceinline__ uint4 load(int k) const {
+      typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff + (uint32_t)k * step, 0, 0);
+      return make_uint4(v[0], v[1], v[2], v[3]);
+    }
+  };
 
-struct FastSrc {
-  __amdgpu_buffer_rsrc_t rsrc;
-  uint32_t voff;  // byte offset of the thread's chunk in box row r0 (2^31: never in range)
-  uint32_t step;  // bytes of kStep frame rows (wave-uniform)
-};
-
-__device__ __forceinline__ uint4 fast_load(const FastSrc& fs, int k) {
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(fs.rsrc, fs.voff + (uint32_t)k * fs.step, 0, 0);
-  return make_uint4(v[0], v[1], v[2], v[3]);
-}
-
-template <class Cfg>
-__device__ __forceinline__ FastSrc fast_stage_issue(const uint16_t* __restrict__ S, int ax0, int sy0, int cpr,
-                                                    int rows, int H, int W, int tid,
-                                                    uint4 (&chunk)[FastStage<Cfg>::kPasses]) {
-  const int r0 = tid / kFastChunks, c = tid - r0 * kFastChunks;
-  const int gx = ax0 + 8 * c;
-  const bool col_ok = c < cpr && (unsigned)gx < (unsigned)W && tid < FastStage<Cfg>::kUsed;
-  FastSrc fs;
-  // |sy0 + r0| and W fit 24 bits; the byte offset of a row above the frame wraps (see above)
-  fs.voff = col_ok ? 2u * (uint32_t)(__mul24(sy0 + r0, W) + gx) : 0x80000000u;
-  fs.step = 2u * FastStage<Cfg>::kStep * (uint32_t)W;
-  fs.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(S), 0, 2 * min(H, sy0 + rows) * W, 0x00020000);
+  static __device__ __forceinline__ void issue(const uint16_t* __restrict__ S, const TilePlan& tp, int H, int W,
+                                               int tid, Loads& l) {
+    const int r0 = tid / kFastChunks, c = tid - r0 * kFastChunks;
+    const int gx = tp.ax0 + 8 * c;
+    const bool col_ok = c < (tp.pitch() >> 3) && (unsigned)gx < (unsigned)W && tid < kUsed;
+    // |sy0 + r0| and W fit 24 bits; the byte offset of a row above the frame wraps (see above)
+    l.voff = col_ok ? 2u * (uint32_t)(__mul24(tp.sy0 + r0, W) + gx) : 0x80000000u;
+    l.step = 2u * kStep * (uint32_t)W;
+    l.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(S), 0, 2 * min(H, tp.sy0 + tp.rows()) * W,
+                                               0x00020000);
 #pragma unroll
-  for (int k = 0; k < FastStage<Cfg>::kPasses; ++k) chunk[k] = fast_load(fs, k);
-  return fs;
-}
-
-__device__ __forceinline__ uint32_t bright_chunks(const uint4& v) {
-  return __builtin_popcountll(__builtin_amdgcn_ballot_w64(((v.x | v.y | v.z | v.w) & 0xc000c000u) != 0));
-}
-
-// Lands the passes in LDS and returns the wave's count of bright (>= 16384) chunks.  Rows
-// below the box and chunks right of its pitch land as zeros (never read).
-template <class Cfg>
-__device__ __forceinline__ uint32_t fast_stage_land(uint16_t* stile, const FastSrc& fs, int rows, int tid,
-                                                    const uint4 (&chunk)[FastStage<Cfg>::kPasses]) {
-  using St = FastStage<Cfg>;
-  uint4* slot = reinterpret_cast<uint4*>(stile) + tid;
-  uint32_t nb = 0;
-  if (tid < St::kUsed) {
-#pragma unroll
-    for (int k = 0; k < St::kPasses; ++k) slot[k * St::kUsed] = chunk[k];
+    for (int k = 0; k < kPasses; ++k) l.chunk[k] = l.load(k);
   }
+
+  // Lands the passes in LDS and returns the wave's count of bright (>= 16384) chunks.  Rows
+  // below the box and chunks right of its pitch land as zeros (never read).
+  static __device__ __forceinline__ uint32_t land(uint16_t* stile, const TilePlan& tp, int tid, const Loads& l) {
+    uint4* slot = reinterpret_cast<uint4*>(stile) + tid;
+    uint32_t nb = 0;
+    if (tid < kUsed) {
 #pragma unroll
-  for (int k = 0; k < St::kPasses; ++k) nb += bright_chunks(chunk[k]);
-  if (St::kTailRows > 0 && rows > St::kPasses * St::kStep) {  // wave-uniform
-    const uint4 t = fast_load(fs, St::kPasses);  // rows past the box are out of range: zeros
-    if (tid < St::kTailRows * kFastChunks) slot[St::kPasses * St::kUsed] = t;
-    nb += bright_chunks(t);
+      for (int k = 0; k < kPasses; ++k) slot[k * kUsed] = l.chunk[k];
+    }
+#pragma unroll
+    for (int k = 0; k < kPasses; ++k) nb += bright_chunks(l.chunk[k]);
+    if (kTailRows > 0 && tp.rows() > kPasses * kStep) {  // wave-uniform
+      const uint4 t = l.load(kPasses);  // rows past the box are out of range: zeros
+      if (tid < kTailRows * kFastChunks) slot[kPasses * kUsed] = t;
+      nb += bright_chunks(t);
+    }
+    return nb;
   }
-  return nb;
-}
+};
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -365,18 +385,22 @@ enum FastBlend {
 // taps then touch most rows (lab figures: DESIGN 4 K3).
 constexpr int kBrightShare = 20;  // bright chunks * kBrightShare > box chunks -> kBright
 
-// Output rows of a mode-3 tile, with the per-row overheads of output_rows removed: row
-// origins are scalar, the lower tap row is an immediate LDS offset, the store is a buffer
-// store with the row offset in soffset.
+// Output rows of a mode-3 tile over its C planes, with the per-row overheads of output_rows
+// removed: row origins are scalar, the lower tap row and the other planes are immediate LDS
+// offsets (the coordinate work of a pixel is shared by its channels), the store is one b32 /
+// b96 / b128 buffer store per lane and row with the row offset in soffset.  The blend is
+// decided once per tile and the rows to make again over every channel's sums.
 // INTERIOR: the tile lies inside the frame (every row exists, every lane's pixel pair is
 // stored), so the rows carry no bounds test and no store mask.
-template <class Cfg, int BLEND, bool INTERIOR>
+template <class Cfg, int C, int BLEND, bool INTERIOR>
 __device__ __forceinline__ void fast_rows(const uint16_t* stile, const int2* __restrict__ rt, int ox, int oy,
                                           uint16_t* __restrict__ Dst, int H, int W, int xb, int yb, int wave, int lane,
                                           const int (&ad)[2], const int (&bd)[2]) {
-  const uint32_t xoff = 2u * (uint32_t)(xb + 2 * lane);  // byte offset of the lane's pixel pair
-  const bool store_ok = INTERIOR || xb + 2 * lane + 2 <= W;  // W is even here
-  const __amdgpu_buffer_rsrc_t dst_rsrc = __builtin_amdgcn_make_buffer_rsrc(Dst, 0, 2 * H * W, 0x00020000);
+  static_assert(C == 1 || C == 3 || C == 4, "planar fast path: gray / RGB / RGBA");
+  constexpr int kPlane = Fast<Cfg, C>::kPlane;
+  const uint32_t xoff = 2u * C * (uint32_t)(xb + 2 * lane);  // byte offset of the lane's pixel pair
+  const bool store_ok = INTERIOR || xb + 2 * lane + 2 <= W;   // W is a multiple of 8 here
+  const __amdgpu_buffer_rsrc_t dst_rsrc = __builtin_amdgcn_make_buffer_rsrc(Dst, 0, 2 * C * H * W, 0x00020000);
   int2 org[Cfg::kTileH / 4];  // all row origins up front (scalar loads; the table is padded)
 #pragma unroll
   for (int i = 0; i < Cfg::kTileH / 4; ++i) org[i] = rt[i];
@@ -394,186 +418,6 @@ __device__ __forceinline__ void fast_rows(const uint16_t* stile, const int2* __r
   typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
   const u16x2 pitch2 = {(unsigned short)2, (unsigned short)(2 * kFastPitch)};
   const char* sbytes = reinterpret_cast<const char*>(stile);
-  // the lane's two pixels of a row with the scaled origin (X0, Y0): four taps and fractions each
-  auto row_taps = [&](uint32_t X0, uint32_t Y0, uint32_t(&v)[2][4], uint32_t(&fx)[2], uint32_t(&fy)[2]) {
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      const uint32_t tX = X0 + ad6[p], tY = Y0 + bd6[p];
-      fx[p] = bfe_11_5(tX);
-      fy[p] = bfe_11_5(tY);
-      const uint32_t cr = __builtin_amdgcn_perm(tY, tX, 0x07060302u);  // (column, row) as u16 x 2
-      const uint32_t off = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, cr), pitch2, 0u, false);
-      const uint16_t* t = reinterpret_cast<const uint16_t*>(sbytes + off);
-      v[p][0] = t[0];
-      v[p][1] = t[1];
-      v[p][2] = t[kFastPitch];
-      v[p][3] = t[kFastPitch + 1];
-    }
-  };
-  auto store_row = [&](const f32x2& q, int y) {
-    const uint32_t out = __builtin_amdgcn_perm(__float_as_uint(q[1]), __float_as_uint(q[0]), 0x05040100u);
-    // aux 2 = nontemporal: the aligned frame is written once and not re-read here
-    if (store_ok) __builtin_amdgcn_raw_buffer_store_b32(out, dst_rsrc, xoff, 2 * y * W, 2);
-  };
-  uint32_t redo = 0;  // kMixed: bit i = the wave's row i waits for the float blend (scalar)
-#pragma unroll
-  for (int i = 0; i < Cfg::kTileH / 4; ++i) {
-    const int y = yb + wave + 4 * i;  // wave-uniform
-    if (!INTERIOR && y >= H) break;
-    const uint32_t X0 = (uint32_t)(org[i].x - ox) << 6, Y0 = (uint32_t)(org[i].y - oy) << 6;  // scalar
-    uint32_t v[2][4], fx[2], fy[2];
-    row_taps(X0, Y0, v, fx, fy);
-    f32x2 q;
-    if constexpr (BLEND == kBright) {
-      q = blend_float2(v, fx, fy);
-    } else {
-      uint32_t Sp[2];
-#pragma unroll
-      for (int p = 0; p < 2; ++p) {
-        const uint32_t ax = 32 - fx[p], ay = 32 - fy[p];
-        uint32_t h0 = __umul24(v[p][0], ax) + __umul24(v[p][1], fx[p]);
-        uint32_t h1 = __umul24(v[p][2], ax) + __umul24(v[p][3], fx[p]);
-        asm volatile("" : "+v"(h0), "+v"(h1));  // keep the separable form (see output_rows)
-        Sp[p] = __umul24(h0, ay) + __umul24(h1, fy[p]);
-        q[p] = (float)Sp[p];
-      }
-      // rint(fl(S) / 1024) in the low bits: fl(S) + 1.5 * 2^33 rounds (half to even) to a
-      // multiple of 1024, the float's unit in the last place there
-      q += 0x1.8p33f;
-      if constexpr (BLEND == kMixed) {
-        // wave-uniform, two levels: rows with no sum >= 2^24 (most) pay one OR and one
-        // compare; of the others only those with a sum near a rounding tie are left out
-        // here and made by the float loop below (the row loop itself stays branch-lean)
-        if (__builtin_amdgcn_ballot_w64(((Sp[0] | Sp[1]) >> 24) != 0) != 0) {
-          if (__builtin_amdgcn_ballot_w64(((int)near_tie(Sp[0]) | (int)near_tie(Sp[1])) != 0) != 0) {
-            redo |= 1u << i;
-            continue;
-          }
-        }
-      }
-    }
-    store_row(q, y);
-  }
-  if constexpr (BLEND == kMixed) {
-    while (redo) {  // the rows left out above (each written once, here): OpenCV's float blend
-      const int i = __builtin_ctz(redo);
-      redo &= redo - 1;
-      const int2 o = rt[i];
-      uint32_t v[2][4], fx[2], fy[2];
-      row_taps((uint32_t)(o.x - ox) << 6, (uint32_t)(o.y - oy) << 6, v, fx, fy);
-      store_row(blend_float2(v, fx, fy), yb + wave + 4 * i);
-    }
-  }
-}
-
-// Fast staged path for C = 3 / 4 (mode 3 of a multi-channel frame, round 4).  The
-// interleaved box is de-interleaved while it lands: each thread loads one 8-pixel group of
-// a box row (C 16-byte chunks, 16-byte aligned because ax0 and W are multiples of 8) and
-// writes C planar 16-byte pieces (v_perm_b32 pairs), one per channel plane, at the fixed
-// pitch.  A pixel's taps then sit at the same offset in every plane (immediate offsets), so
-// the coordinate work of a pixel is shared by its C channels, and each lane's C output
-// dwords (pixels 2l, 2l+1) leave in ONE 12- / 16-byte store: a wave's store covers 768 /
-// 1024 contiguous bytes of the row.  The general multi-channel path (mode 0) reads
-// interleaved taps with per-channel addressing and stores C separate dwords per lane at a
-// 12-byte lane stride (round 3: 148 VALU, 49 SALU, 25 LDS instructions per wave row at c4).
-template <class Cfg, int C>
-struct FastC {
-  static constexpr int kPitch = 144;  // plane row pitch in pixels (192: fewer bank conflicts, same time)
-  static constexpr int kRows = (Cfg::kLdsElems - 8) / (C * kPitch);      // the last 16 bytes: flags
-  static constexpr int kPlane = kRows * kPitch;                          // elements per channel plane
-  static constexpr int kFlagWord = Cfg::kLdsElems / 2 - 4;
-  static constexpr int kGroups = kPitch / 8;                             // 8-pixel groups per staged row
-  static constexpr int kPasses = (kRows * kGroups + kThreads - 1) / kThreads;
-  static_assert(C * kPlane <= 2 * kFlagWord, "planes overlap the flag words");
-};
-
-template <class Cfg, int C>
-__device__ __forceinline__ void fastc_stage_issue(const uint16_t* __restrict__ S, int ax0, int sy0, int gpr, int rows,
-                                                  int H, int W, int tid,
-                                                  uint4 (&g)[FastC<Cfg, C>::kPasses][C]) {
-#pragma unroll
-  for (int k = 0; k < FastC<Cfg, C>::kPasses; ++k) {
-    const int q = tid + kThreads * k;
-    const int r = q / FastC<Cfg, C>::kGroups, c = q - r * FastC<Cfg, C>::kGroups;
-    const int gy = sy0 + r, gx = ax0 + 8 * c;
-    const bool ok = r < rows && c < gpr && (unsigned)gx < (unsigned)W && (unsigned)gy < (unsigned)H;
-#pragma unroll
-    for (int j = 0; j < C; ++j) g[k][j] = make_uint4(0u, 0u, 0u, 0u);
-    if (ok) {
-      const uint4* src = reinterpret_cast<const uint4*>(S + ((size_t)gy * W + gx) * C);
-#pragma unroll
-      for (int j = 0; j < C; ++j) g[k][j] = src[j];
-    }
-  }
-}
-
-// word i of plane k of an 8-pixel group: elements C (2i) + k and C (2i + 1) + k of the
-// interleaved group (dwords d[e / 2], halves e % 2), as one v_perm_b32
-template <int C, int K, int I>
-__device__ __forceinline__ uint32_t plane_word(const uint32_t (&d)[4 * C]) {
-  constexpr int e0 = C * 2 * I + K, e1 = C * (2 * I + 1) + K;
-  constexpr uint32_t sel = ((e0 & 1) ? 0x0302u : 0x0100u) | ((e1 & 1) ? 0x07060000u : 0x05040000u);
-  return __builtin_amdgcn_perm(d[e1 / 2], d[e0 / 2], sel);
-}
-
-template <int C, int K>
-__device__ __forceinline__ uint4 plane_piece(const uint32_t (&d)[4 * C]) {
-  return make_uint4(plane_word<C, K, 0>(d), plane_word<C, K, 1>(d), plane_word<C, K, 2>(d), plane_word<C, K, 3>(d));
-}
-
-template <class Cfg, int C>
-__device__ __forceinline__ uint32_t fastc_stage_land(uint16_t* stile, int gpr, int rows, int tid,
-                                                     const uint4 (&g)[FastC<Cfg, C>::kPasses][C]) {
-  uint32_t nb = 0;  // bright (>= 16384) groups of this wave
-#pragma unroll
-  for (int k = 0; k < FastC<Cfg, C>::kPasses; ++k) {
-    const int q = tid + kThreads * k;
-    const int r = q / FastC<Cfg, C>::kGroups, c = q - r * FastC<Cfg, C>::kGroups;
-    uint32_t d[4 * C], any = 0;  // the group's 8 C elements, two per dword
-#pragma unroll
-    for (int j = 0; j < C; ++j) {
-      d[4 * j] = g[k][j].x;
-      d[4 * j + 1] = g[k][j].y;
-      d[4 * j + 2] = g[k][j].z;
-      d[4 * j + 3] = g[k][j].w;
-      any |= g[k][j].x | g[k][j].y | g[k][j].z | g[k][j].w;
-    }
-    nb += __builtin_popcountll(__builtin_amdgcn_ballot_w64((any & 0xc000c000u) != 0));
-    if (r < rows && c < gpr) {
-      uint4* dst = reinterpret_cast<uint4*>(stile + r * FastC<Cfg, C>::kPitch + 8 * c);
-      dst[0] = plane_piece<C, 0>(d);
-      dst[FastC<Cfg, C>::kPlane / 8] = plane_piece<C, 1>(d);
-      dst[2 * FastC<Cfg, C>::kPlane / 8] = plane_piece<C, 2>(d);
-      if constexpr (C == 4) dst[3 * FastC<Cfg, C>::kPlane / 8] = plane_piece<C, 3>(d);
-    }
-  }
-  return nb;
-}
-
-// Output rows of a multi-channel mode-3 tile: fast_rows with C planes (same coordinate
-// scheme, same three blends, the blend decided once per tile and the rows to make again
-// over every channel's sums) and one b96 / b128 buffer store per lane and row.
-template <class Cfg, int C, int BLEND, bool INTERIOR>
-__device__ __forceinline__ void fastc_rows(const uint16_t* stile, const int2* __restrict__ rt, int ox, int oy,
-                                           uint16_t* __restrict__ Dst, int H, int W, int xb, int yb, int wave,
-                                           int lane, const int (&ad)[2], const int (&bd)[2]) {
-  static_assert(C == 3 || C == 4, "planar fast path: RGB / RGBA");
-  constexpr int kPlane = FastC<Cfg, C>::kPlane, kPitch = FastC<Cfg, C>::kPitch;
-  const uint32_t xoff = 2u * C * (uint32_t)(xb + 2 * lane);  // byte offset of the lane's pixel pair
-  const bool store_ok = INTERIOR || xb + 2 * lane + 2 <= W;   // W is a multiple of 8 here
-  const __amdgpu_buffer_rsrc_t dst_rsrc = __builtin_amdgcn_make_buffer_rsrc(Dst, 0, 2 * C * H * W, 0x00020000);
-  int2 org[Cfg::kTileH / 4];
-#pragma unroll
-  for (int i = 0; i < Cfg::kTileH / 4; ++i) org[i] = rt[i];
-  uint32_t ad6[2], bd6[2];
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    ad6[p] = (uint32_t)ad[p] << 6;
-    bd6[p] = (uint32_t)bd[p] << 6;
-  }
-  typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-  const u16x2 pitch2 = {(unsigned short)2, (unsigned short)(2 * kPitch)};
-  const char* sbytes = reinterpret_cast<const char*>(stile);
   // the lane's two pixels of a row with the scaled origin (X0, Y0): C x four taps, fractions
   auto row_taps = [&](uint32_t X0, uint32_t Y0, uint32_t(&v)[C][2][4], uint32_t(&fx)[2], uint32_t(&fy)[2]) {
 #pragma unroll
@@ -588,15 +432,19 @@ __device__ __forceinline__ void fastc_rows(const uint16_t* stile, const int2* __
       for (int k = 0; k < C; ++k) {
         v[k][p][0] = t[k * kPlane];
         v[k][p][1] = t[k * kPlane + 1];
-        v[k][p][2] = t[k * kPlane + kPitch];
-        v[k][p][3] = t[k * kPlane + kPitch + 1];
+        v[k][p][2] = t[k * kPlane + kFastPitch];
+        v[k][p][3] = t[k * kPlane + kFastPitch + 1];
       }
     }
   };
   // the lane's 2 C channel values in interleaved order, two per dword
+  // (aux 2 = nontemporal: the aligned frame is written once and not re-read here)
   auto store_row = [&](const f32x2(&q)[C], int y) {
 #define KCMC_Q(px, ch) __float_as_uint(q[ch][px])
-    if constexpr (C == 3) {
+    if constexpr (C == 1) {
+      const uint32_t o = __builtin_amdgcn_perm(KCMC_Q(1, 0), KCMC_Q(0, 0), 0x05040100u);
+      if (store_ok) __builtin_amdgcn_raw_buffer_store_b32(o, dst_rsrc, xoff, 2 * C * y * W, 2);
+    } else if constexpr (C == 3) {
       typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
       const u32x3 o = {__builtin_amdgcn_perm(KCMC_Q(0, 1), KCMC_Q(0, 0), 0x05040100u),
                        __builtin_amdgcn_perm(KCMC_Q(1, 0), KCMC_Q(0, 2), 0x05040100u),
@@ -638,11 +486,15 @@ __device__ __forceinline__ void fastc_rows(const uint16_t* stile, const int2* __
           hi |= Sp[k][p];
           q[k][p] = (float)Sp[k][p];
         }
-        q[k] += 0x1.8p33f;  // rint(fl(S) / 1024) in the low bits (fast_rows)
+        // rint(fl(S) / 1024) in the low bits: fl(S) + 1.5 * 2^33 rounds (half to even) to a
+        // multiple of 1024, the float's unit in the last place there
+        q[k] += 0x1.8p33f;
       }
       if constexpr (BLEND == kMixed) {
-        // wave-uniform, two levels over every channel's sums; rows with a sum near a rounding
-        // tie are left to the float loop below (fast_rows)
+        // wave-uniform, two levels over every channel's sums: rows with no sum >= 2^24 (most)
+        // pay one OR and one compare; of the others only those with a sum near a rounding tie
+        // are left out here and made by the float loop below (the row loop itself stays
+        // branch-lean)
         if (__builtin_amdgcn_ballot_w64((hi >> 24) != 0) != 0) {
           int tie = 0;
 #pragma unroll
@@ -686,58 +538,19 @@ __device__ __forceinline__ void lds_sentinel(uint16_t* stile, int tid) {
 #define KCMC_LDS_SENTINEL(stile, elems, tid) ((void)0)
 #endif
 
-// Per-tile plan made by warp_plan_kernel.
-struct TilePlan {
-  int mode, ax0, sy0;
-  int pitch_rows;  // pitch | rows << 16
-};
-
-__device__ __forceinline__ Box unpack(const TilePlan& t) {
-  Box b;
-  b.mode = t.mode;
-  b.ax0 = t.ax0;
-  b.sy0 = t.sy0;
-  b.pitch = t.pitch_rows & 0xffff;
-  b.rows = t.pitch_rows >> 16;
-  return b;
-}
-
-// Per-thread coordinates of one tile (WarpAffineInvoker): adelta/bdelta of the lane's two
-// columns, and in lane i < kTileH/4 the row origins X0/Y0 of the wave's i-th row.  For a
-// staged tile the box origin (ox, oy) is folded into the row origins (a multiple of 1024
-// in fixed point, so the fractional bits are unchanged): coordinates are box-relative.
-// Columns past the frame edge reuse the last valid column's coordinates so that their
-// (never stored) taps stay inside the box.
-__device__ __forceinline__ void lane_cols(const double* __restrict__ M, int xb, int W, int lane, int (&ad)[2],
-                                          int (&bd)[2]) {
-#pragma unroll
-  for (int q = 0; q < 2; ++q) {
-    const int x = min(xb + 2 * lane + q, W - 1);
-    ad[q] = cv_round(M[0] * x * 1024);
-    bd[q] = cv_round(M[3] * x * 1024);
-  }
-}
-
-template <class Cfg>
-__device__ __forceinline__ void lane_coords(const double* __restrict__ M, int xb, int yb, int W, int wave, int lane,
-                                            int ox, int oy, int (&ad)[2], int (&bd)[2], int& X0v, int& Y0v) {
-  lane_cols(M, xb, W, lane, ad, bd);
-  const int y = yb + wave + 4 * min(lane, Cfg::kTileH / 4 - 1);
-  X0v = cv_round((M[1] * y + M[2]) * 1024) + 16 - ox * 1024;
-  Y0v = cv_round((M[4] * y + M[5]) * 1024) + 16 - oy * 1024;
-}
-
 // Output rows of one tile on one path (0: LDS-staged box, 1: zeros, 2: direct gather).
-// Wave w makes rows w, w + 4, ...; lane l pixels x = xb + 2l, xb + 2l + 1.
+// Wave w makes rows w, w + 4, ...; lane l pixels x = xb + 2l, xb + 2l + 1.  ad / bd: the
+// lane's column deltas (lane_columns); X0v / Y0v: in lane i the origins of the wave's i-th
+// row, box-relative for a staged tile (row_origins).
 template <class Cfg, int C, int MODE>
-__device__ __forceinline__ void output_rows(const uint16_t* stile, const Box& box, const uint16_t* __restrict__ S,
-                                            uint16_t* __restrict__ Dst, int H, int W, int xb, int yb, int wave,
-                                            int lane, const int (&ad)[2], const int (&bd)[2], int X0v, int Y0v) {
-  const int x = xb + 2 * lane;
+__device__ __forceinline__ void output_rows(const uint16_t* stile, const TilePlan& tp, const uint16_t* __restrict__ S,
+                                            uint16_t* __restrict__ Dst, int H, int W, const TileId& t,
+                                            const int (&ad)[2], const int (&bd)[2], int X0v, int Y0v) {
+  const int x = t.xb + 2 * t.lane, pitch = tp.pitch();
   const bool pair_store = C == 1 && (W & 1) == 0 && x + 2 <= W;
 #pragma unroll
   for (int i = 0; i < Cfg::kTileH / 4; ++i) {
-    const int y = yb + wave + 4 * i;  // wave-uniform
+    const int y = t.yb + t.wave + 4 * i;  // wave-uniform
     if (y >= H) break;
     const int X0 = __builtin_amdgcn_readlane(X0v, i), Y0 = __builtin_amdgcn_readlane(Y0v, i);
     uint16_t o[2 * C];
@@ -754,13 +567,13 @@ __device__ __forceinline__ void output_rows(const uint16_t* stile, const Box& bo
         const int tX = X0 + ad[p], tY = Y0 + bd[p];
         fx[p] = (tX >> 5) & 31;
         fy[p] = (tY >> 5) & 31;
-        li[p] = __umul24((uint32_t)(tY >> 10), (uint32_t)box.pitch) + (uint32_t)(tX >> 10);
+        li[p] = __umul24((uint32_t)(tY >> 10), (uint32_t)pitch) + (uint32_t)(tX >> 10);
       }
 #pragma unroll
       for (int p = 0; p < 2; ++p)
 #pragma unroll
         for (int k = 0; k < C; ++k) {
-          const int i00 = li[p] * C + k, i10 = i00 + box.pitch * C;
+          const int i00 = li[p] * C + k, i10 = i00 + pitch * C;
           v[p][k][0] = tap(stile, i00);
           v[p][k][1] = tap(stile, i00 + C);
           v[p][k][2] = tap(stile, i10);
@@ -823,18 +636,19 @@ __device__ __forceinline__ void output_rows(const uint16_t* stile, const Box& bo
 }
 
 // One row loop per path (a path-uniform branch inside the loop makes the compiler drain
-// the previous rows' stores with s_waitcnt vmcnt(0) every row).
+// the previous rows' stores with s_waitcnt vmcnt(0) every row).  A function of its own: with
+// the three calls written in the kernel, the RGB / RGBA edge stores keep a dead second pixel
+// (twice the 2-byte stores, two more VGPRs; profiles/warp_linear_shared.md).
 template <class Cfg, int C>
-__device__ __forceinline__ void output_tile(int mode, const uint16_t* stile, const Box& box,
-                                            const uint16_t* __restrict__ S, uint16_t* __restrict__ Dst, int H, int W,
-                                            int xb, int yb, int wave, int lane, const int (&ad)[2], const int (&bd)[2],
-                                            int X0v, int Y0v) {
-  if (mode == 0)
-    output_rows<Cfg, C, 0>(stile, box, S, Dst, H, W, xb, yb, wave, lane, ad, bd, X0v, Y0v);
-  else if (mode == 1)
-    output_rows<Cfg, C, 1>(stile, box, S, Dst, H, W, xb, yb, wave, lane, ad, bd, X0v, Y0v);
+__device__ __forceinline__ void output_tile(const uint16_t* stile, const TilePlan& tp, const uint16_t* __restrict__ S,
+                                            uint16_t* __restrict__ Dst, int H, int W, const TileId& t,
+                                            const int (&ad)[2], const int (&bd)[2], int X0v, int Y0v) {
+  if (tp.mode == 0)
+    output_rows<Cfg, C, 0>(stile, tp, S, Dst, H, W, t, ad, bd, X0v, Y0v);
+  else if (tp.mode == 1)
+    output_rows<Cfg, C, 1>(stile, tp, S, Dst, H, W, t, ad, bd, X0v, Y0v);
   else
-    output_rows<Cfg, C, 2>(stile, box, S, Dst, H, W, xb, yb, wave, lane, ad, bd, X0v, Y0v);
+    output_rows<Cfg, C, 2>(stile, tp, S, Dst, H, W, t, ad, bd, X0v, Y0v);
 }
 
 // (xcd_remap: kcmc_internal.h)
@@ -853,27 +667,18 @@ __global__ __launch_bounds__(256) void warp_plan_kernel(const double* __restrict
                                                         int2* __restrict__ rowtab, int hq) {
   const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
   if (t >= (long long)ntx * nty * n_frames) return;
-  const int f = (int)(t / (ntx * nty)), t2 = (int)(t - (long long)f * ntx * nty);
-  const int tx = t2 % ntx, xb = tx * kTileW, yb = (t2 / ntx) * Cfg::kTileH;
-  double M[6];
-  load_map(Mall, f, inverse_map, M);
-  if (t2 == 0)
-    for (int k = 0; k < 6; ++k) minv[6 * (size_t)f + k] = M[k];
-  Box b = source_box<Cfg, C>(M, xb, yb, H, W);
-  if constexpr (C == 1) {
-    // 2 H W < 2^31: the frame fits the range of the fast path's buffer descriptors
-    if ((W & 7) == 0 && 2ll * H * W < (1ll << 31) && b.mode == 0 && b.pitch <= kFastPitch &&
-        b.rows <= Fast<Cfg>::kRows)
-      b.mode = 3;
-  } else if constexpr (C == 3 || C == 4) {
-    if ((W & 7) == 0 && b.mode == 0 && b.pitch <= FastC<Cfg, C>::kPitch && b.rows <= FastC<Cfg, C>::kRows) b.mode = 3;
-  }
-  if (map_has_nan(M, 6)) b.mode = 1;  // a NaN map (a frame RANSAC could not fit) warps to zeros
-  plan[t] = TilePlan{b.mode, b.ax0, b.sy0, b.pitch | (b.rows << 16)};
-  for (int j = tx; j < Cfg::kTileH && yb + j < H; j += ntx) {
-    const int y = yb + j;
-    rowtab[((size_t)f * 4 + (y & 3)) * hq + (y >> 2)] =
-        make_int2(cv_round((M[1] * y + M[2]) * 1024) + 16, cv_round((M[4] * y + M[5]) * 1024) + 16);
+  const PlanTile p = plan_tile<Cfg::kTileH>(t, Mall, inverse_map, H, W, ntx, nty, minv);
+  TilePlan b = source_box<Cfg, C>(p, H, W);
+  // C == 1, 2 H W < 2^31: the frame fits the range of the fast path's buffer descriptors
+  if ((W & 7) == 0 && (C > 1 || 2ll * H * W < (1ll << 31)) && b.mode == 0 && b.pitch() <= kFastPitch &&
+      b.rows() <= Fast<Cfg, C>::kRows)
+    b.mode = 3;
+  if (map_has_nan(p.M, 6)) b.mode = 1;  // a NaN map (a frame RANSAC could not fit) warps to zeros
+  plan[t] = b;
+  for (int j = p.xb / kTileW; j < Cfg::kTileH && p.yb + j < H; j += ntx) {
+    const int y = p.yb + j;
+    rowtab[((size_t)p.f * 4 + (y & 3)) * hq + (y >> 2)] =
+        make_int2(cv_round((p.M[1] * y + p.M[2]) * 1024) + 16, cv_round((p.M[4] * y + p.M[5]) * 1024) + 16);
   }
 }
 
@@ -886,155 +691,56 @@ __global__ __launch_bounds__(kThreads) __attribute__((target("no-unaligned-acces
     const uint16_t* __restrict__ src, uint16_t* __restrict__ dst, const TilePlan* __restrict__ plan,
     const double* __restrict__ minv, const int2* __restrict__ rowtab, int hq, int H, int W) {
   __shared__ __attribute__((aligned(16))) uint16_t stile[Cfg::kLdsElems];
-  const int ntx = gridDim.x, nty = gridDim.y;
-  const int tile = xcd_remap(blockIdx.x + ntx * (blockIdx.y + nty * blockIdx.z), ntx * nty * gridDim.z);
-  const int f = tile / (ntx * nty);
-  const int t2 = tile - f * ntx * nty;
-  const int xb = (t2 % ntx) * kTileW, yb = (t2 / ntx) * Cfg::kTileH;
+  const TileId t = tile_decode<Cfg::kTileH>();
   const int tid = threadIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-  const uint16_t* S = src + (size_t)f * H * W * C;
-  uint16_t* Dst = dst + (size_t)f * H * W * C;
+  const uint16_t* S = src + (size_t)t.f * H * W * C;
+  uint16_t* Dst = dst + (size_t)t.f * H * W * C;
+  const double* M = minv + 6 * (size_t)t.f;
 
-  Box box = unpack(plan[tile]);
+  const TilePlan tp = plan[t.tile];
   KCMC_LDS_SENTINEL(stile, Cfg::kLdsElems, tid);
-  if constexpr (C == 1) {
-    if (box.mode == 3) {
-      const int cpr = box.pitch >> 3;
-      uint4 fchunk[FastStage<Cfg>::kPasses];
-      const FastSrc fs = fast_stage_issue<Cfg>(S, box.ax0, box.sy0, cpr, box.rows, H, W, tid, fchunk);  // loads first
-      int ad[2], bd[2];
-      lane_cols(minv + 6 * (size_t)f, xb, W, lane, ad, bd);
-      // the box lands; its bright chunks are counted per wave into the flag words
-      const uint32_t nb = fast_stage_land<Cfg>(stile, fs, box.rows, tid, fchunk);
-      uint32_t* flags = reinterpret_cast<uint32_t*>(stile) + Fast<Cfg>::kFlagWord;
-      if (lane == 0) flags[wave] = nb;
-      __syncthreads();
-      const uint4 fl = *reinterpret_cast<const uint4*>(flags);
-      const uint32_t bright = fl.x + fl.y + fl.z + fl.w;
-      const int2* rt = rowtab + ((size_t)f * 4 + wave) * hq + (yb >> 2);
-      const int ox = box.ax0 * 1024, oy = box.sy0 * 1024;
-      const bool interior = yb + Cfg::kTileH <= H && xb + kTileW <= W;
-      if (bright == 0) {
-        if (interior)
-          fast_rows<Cfg, kDark, true>(stile, rt, ox, oy, Dst, H, W, xb, yb, wave, lane, ad, bd);
-        else
-          fast_rows<Cfg, kDark, false>(stile, rt, ox, oy, Dst, H, W, xb, yb, wave, lane, ad, bd);
-      } else if ((int)bright * kBrightShare <= box.rows * (box.pitch >> 3)) {
-        if (interior)
-          fast_rows<Cfg, kMixed, true>(stile, rt, ox, oy, Dst, H, W, xb, yb, wave, lane, ad, bd);
-        else
-          fast_rows<Cfg, kMixed, false>(stile, rt, ox, oy, Dst, H, W, xb, yb, wave, lane, ad, bd);
-      } else {
-        fast_rows<Cfg, kBright, false>(stile, rt, ox, oy, Dst, H, W, xb, yb, wave, lane, ad, bd);
-      }
-      return;
-    }
-  }
-  if constexpr (C == 3 || C == 4) {
-    if (box.mode == 3) {
-      const int gpr = box.pitch >> 3;
-      uint4 g[FastC<Cfg, C>::kPasses][C];
-      fastc_stage_issue<Cfg, C>(S, box.ax0, box.sy0, gpr, box.rows, H, W, tid, g);  // loads first
-      int ad[2], bd[2];
-      lane_cols(minv + 6 * (size_t)f, xb, W, lane, ad, bd);
-      const uint32_t nb = fastc_stage_land<Cfg, C>(stile, gpr, box.rows, tid, g);
-      uint32_t* flags = reinterpret_cast<uint32_t*>(stile) + FastC<Cfg, C>::kFlagWord;
-      if (lane == 0) flags[wave] = nb;
-      __syncthreads();
-      const uint4 fl = *reinterpret_cast<const uint4*>(flags);
-      const uint32_t bright = fl.x + fl.y + fl.z + fl.w;
-      const int2* rt = rowtab + ((size_t)f * 4 + wave) * hq + (yb >> 2);
-      const int ox = box.ax0 * 1024, oy = box.sy0 * 1024;
-      const bool interior = yb + Cfg::kTileH <= H && xb + kTileW <= W;
-      if (bright == 0) {
-        if (interior)
-          fastc_rows<Cfg, C, kDark, true>(stile, rt, ox, oy, Dst, H, W, xb, yb, wave, lane, ad, bd);
-        else
-          fastc_rows<Cfg, C, kDark, false>(stile, rt, ox, oy, Dst, H, W, xb, yb, wave, lane, ad, bd);
-      } else if ((int)bright * kBrightShare <= box.rows * (box.pitch >> 3)) {
-        if (interior)
-          fastc_rows<Cfg, C, kMixed, true>(stile, rt, ox, oy, Dst, H, W, xb, yb, wave, lane, ad, bd);
-        else
-          fastc_rows<Cfg, C, kMixed, false>(stile, rt, ox, oy, Dst, H, W, xb, yb, wave, lane, ad, bd);
-      } else {
-        fastc_rows<Cfg, C, kBright, false>(stile, rt, ox, oy, Dst, H, W, xb, yb, wave, lane, ad, bd);
-      }
-      return;
-    }
-  }
-  const bool vec_stage = (C == 1) && ((W & 7) == 0);
-  uint4 chunk[Cfg::kRowPasses];
-  uint4 cchunk[C > 1 ? VecC<Cfg, C>::kPasses : 1];
-  if (box.mode == 0 && vec_stage) stage_issue<Cfg>(S, box, H, W, tid, chunk);  // loads first
-  if constexpr (C > 1) {
-    if (box.mode == 0 && (W & 7) == 0) stage_vec_c_issue<Cfg, C>(S, box, H, W, tid, cchunk);
-  }
-  int ad[2], bd[2], X0v, Y0v;  // overlaps the loads
-  lane_coords<Cfg>(minv + 6 * (size_t)f, xb, yb, W, wave, lane, box.mode == 0 ? box.ax0 : 0,
-                   box.mode == 0 ? box.sy0 : 0, ad, bd, X0v, Y0v);
-  if (box.mode == 0) {
-    if (vec_stage) {
-      stage_land<Cfg>(stile, box, tid, chunk);
-    } else if (C > 1 && (W & 7) == 0) {
-      if constexpr (C > 1) stage_vec_c_land<Cfg, C>(stile, box, tid, cchunk);
+  int ad[2], bd[2];
+  if (tp.mode == 3) {
+    using F = Fast<Cfg, C>;
+    typename F::Loads loads;
+    F::issue(S, tp, H, W, tid, loads);  // loads first
+    lane_columns(M, t.xb, t.lane, W, ad, bd);
+    // the box lands; its bright chunks are counted per wave into the flag words
+    const uint32_t nb = F::land(stile, tp, tid, loads);
+    uint32_t* flags = reinterpret_cast<uint32_t*>(stile) + F::kFlagWord;
+    if (t.lane == 0) flags[t.wave] = nb;
+    __syncthreads();
+    const uint4 fl = *reinterpret_cast<const uint4*>(flags);
+    const uint32_t bright = fl.x + fl.y + fl.z + fl.w;
+    const int2* rt = rowtab + ((size_t)t.f * 4 + t.wave) * hq + (t.yb >> 2);
+    const int ox = tp.ax0 * 1024, oy = tp.sy0 * 1024;
+    const bool interior = t.yb + Cfg::kTileH <= H && t.xb + kTileW <= W;
+#define KCMC_FAST_ROWS(blend, inside) \
+  fast_rows<Cfg, C, blend, inside>(stile, rt, ox, oy, Dst, H, W, t.xb, t.yb, t.wave, t.lane, ad, bd)
+    if (bright == 0) {
+      if (interior)
+        KCMC_FAST_ROWS(kDark, true);
+      else
+        KCMC_FAST_ROWS(kDark, false);
+    } else if ((int)bright * kBrightShare <= tp.rows() * (tp.pitch() >> 3)) {
+      if (interior)
+        KCMC_FAST_ROWS(kMixed, true);
+      else
+        KCMC_FAST_ROWS(kMixed, false);
     } else {
-      stage_scalar<C>(S, stile, box, H, W, tid);
+      KCMC_FAST_ROWS(kBright, false);
     }
+#undef KCMC_FAST_ROWS
+    return;
   }
+  BoxLoads<Cfg, C> loads;
+  box_issue<Cfg, C>(S, tp, H, W, loads);  // loads first
+  int X0v, Y0v;  // overlaps the loads
+  lane_columns(M, t.xb, t.lane, W, ad, bd);
+  row_origins<Cfg::kTileH>(M, t, tp, X0v, Y0v);
+  box_land<Cfg, C>(stile, S, tp, H, W, loads);
   __syncthreads();
-  output_tile<Cfg, C>(box.mode, stile, box, S, Dst, H, W, xb, yb, wave, lane, ad, bd, X0v, Y0v);
-}
-
-// Row-origin table entries per (frame, y & 3): padded so that a wave's scalar loads of
-// its kTileH / 4 entries stay inside the frame's block.
-inline int rowtab_hq(int H) { return ceil_div(H, 4) + 16; }
-
-template <class Cfg>
-size_t warp_workspace_bytes(int n_frames, int H, int W) {
-  const size_t tiles = (size_t)ceil_div(W, kTileW) * ceil_div(H, Cfg::kTileH) * n_frames;
-  return tiles * sizeof(TilePlan) + (size_t)n_frames * 6 * sizeof(double) +
-         (size_t)n_frames * 4 * rowtab_hq(H) * sizeof(int2);
-}
-
-// Workspace layout of the affine warp: minv [F, 6] f64, rowtab [F, 4, hq] int2, plan [tiles].
-template <class Cfg>
-struct WarpWs {
-  double* minv;
-  int2* rowtab;
-  TilePlan* plan;
-  int hq;
-  WarpWs(void* ws, int n_frames, int H) {
-    minv = static_cast<double*>(ws);
-    hq = rowtab_hq(H);
-    rowtab = reinterpret_cast<int2*>(minv + 6 * (size_t)n_frames);
-    plan = reinterpret_cast<TilePlan*>(rowtab + (size_t)n_frames * 4 * hq);
-  }
-};
-
-template <int C, class Cfg = typename CfgFor<C>::type>
-void launch_warp_plan(const double* M, int n_frames, int H, int W, int inverse_map, void* ws, hipStream_t s) {
-  const int ntx = ceil_div(W, kTileW), nty = ceil_div(H, Cfg::kTileH);
-  const long long tiles = (long long)ntx * nty * n_frames;
-  const WarpWs<Cfg> w(ws, n_frames, H);
-  hipLaunchKernelGGL((warp_plan_kernel<C, Cfg>), dim3((unsigned)((tiles + 255) / 256)), dim3(256), 0, s, M, n_frames,
-                     H, W, inverse_map, ntx, nty, w.plan, w.minv, w.rowtab, w.hq);
-}
-
-template <int C, class Cfg = typename CfgFor<C>::type>
-void launch_warp_tiles(const uint16_t* src, uint16_t* dst, int n_frames, int H, int W, const void* ws, hipStream_t s) {
-  const int ntx = ceil_div(W, kTileW), nty = ceil_div(H, Cfg::kTileH);
-  const WarpWs<Cfg> w(const_cast<void*>(ws), n_frames, H);
-  hipLaunchKernelGGL((warp_affine_u16_kernel<C, Cfg>), dim3(ntx, nty, n_frames), dim3(kThreads), 0, s, src,
-                     dst, w.plan, w.minv, w.rowtab, w.hq, H, W);
-}
-
-// Plan + tile launches on `s`; ws holds warp_workspace_bytes<Cfg>(n_frames, H, W) bytes.
-template <int C, class Cfg = typename CfgFor<C>::type>
-void launch_warp(const uint16_t* src, uint16_t* dst, const double* M, int n_frames, int H, int W, int inverse_map,
-                 void* ws, hipStream_t s) {
-  launch_warp_plan<C, Cfg>(M, n_frames, H, W, inverse_map, ws, s);
-  launch_warp_tiles<C, Cfg>(src, dst, n_frames, H, W, ws, s);
+  output_tile<Cfg, C>(stile, tp, S, Dst, H, W, t, ad, bd, X0v, Y0v);
 }
 
 // ================================================================ warpPerspective
@@ -1087,7 +793,7 @@ struct PerspTab {
 // the tile's image is the convex hull of its corner images; one pixel of margin on each
 // side absorbs the 1/32-px rounding and the second tap.  Otherwise: direct gather.
 template <class Cfg, int C>
-__device__ __forceinline__ Box persp_box(const double* M, int xb, int yb, int H, int W) {
+__device__ __forceinline__ TilePlan persp_box(const double* M, int xb, int yb, int H, int W) {
   const int xl = min(xb + kTileW, W) - 1, yl = min(yb + Cfg::kTileH, H) - 1;
   const int cx[4] = {xb, xl, xb, xl}, cy[4] = {yb, yb, yl, yl};
   double mnx = INFINITY, mxx = -INFINITY, mny = INFINITY, mxy = -INFINITY;
@@ -1107,25 +813,10 @@ __device__ __forceinline__ Box persp_box(const double* M, int xb, int yb, int H,
     mny = fmin(mny, sy);
     mxy = fmax(mxy, sy);
   }
-  Box b;
-  b.mode = 2;
-  b.ax0 = b.sy0 = b.pitch = b.rows = 0;
   const double lim = 30000.0;  // keep clear of saturate_cast<short> on coordinates
-  if (!(pos || neg) || !(mnx > -lim && mxx < lim && mny > -lim && mxy < lim)) return b;
-  const long long sx0 = (long long)floor(mnx) - 1, sx1 = (long long)floor(mxx) + 2;
-  const long long sy0 = (long long)floor(mny) - 1, sy1 = (long long)floor(mxy) + 2;
-  const long long ax0 = (sx0 >> 3) << 3;
-  const long long pitch = ((sx1 - ax0 + 1) + 7) & ~7ll;
-  const long long rows = sy1 - sy0 + 1;
-  if (sx1 < 0 || sx0 > W - 1 || sy1 < 0 || sy0 > H - 1)
-    b.mode = 1;
-  else if (wrange && pitch <= kMaxPitch && rows <= 8 * Cfg::kRowPasses && pitch * rows * C <= PerspTab<Cfg>::kBoxElems)
-    b.mode = 0;
-  b.ax0 = (int)ax0;
-  b.sy0 = (int)sy0;
-  b.pitch = (int)pitch;
-  b.rows = (int)rows;
-  return b;
+  if (!(pos || neg) || !(mnx > -lim && mxx < lim && mny > -lim && mxy < lim)) return TilePlan{2, 0, 0, 0};
+  return box_plan<Cfg, C>((long long)floor(mnx) - 1, (long long)floor(mxx) + 2, (long long)floor(mny) - 1,
+                          (long long)floor(mxy) + 2, H, W, true, wrange, PerspTab<Cfg>::kBoxElems);
 }
 
 template <int C, class Cfg>
@@ -1144,9 +835,9 @@ __global__ __launch_bounds__(256) void persp_plan_kernel(const double* __restric
   }
   if (t2 == 0)
     for (int k = 0; k < 9; ++k) minv[9 * (size_t)f + k] = M[k];
-  Box b = persp_box<Cfg, C>(M, xb, yb, H, W);
+  TilePlan b = persp_box<Cfg, C>(M, xb, yb, H, W);
   if (map_has_nan(M, 9)) b.mode = 1;  // a NaN map (a frame RANSAC could not fit) warps to zeros
-  plan[t] = TilePlan{b.mode, b.ax0, b.sy0, b.pitch | (b.rows << 16)};
+  plan[t] = b;
 }
 
 // remapBilinear's blend of four taps: exact integer evaluation, with the float-faithful
@@ -1225,10 +916,10 @@ __device__ __forceinline__ void persp_px(double X0, double Y0, double W0, double
 // DARK (MODE 0, C == 1): every staged value is < 16384, so the exact integer blend needs no
 // range check (as kDark of the affine fast path).
 template <class Cfg, int C, int MODE, bool TAB, bool DARK = false>
-__device__ __forceinline__ void persp_rows(const uint16_t* stile, const Box& box, const uint16_t* __restrict__ S,
-                                           uint16_t* __restrict__ Dst, const double* M, int H, int W, int xb, int yb,
-                                           int wave, int lane, int bw0, const double* ptab) {
-  const int x = xb + 2 * lane;
+__device__ __forceinline__ void persp_rows(const uint16_t* stile, const TilePlan& tp, const uint16_t* __restrict__ S,
+                                           uint16_t* __restrict__ Dst, const double* M, int H, int W, const TileId& t,
+                                           int bw0, const double* ptab) {
+  const int x = t.xb + 2 * t.lane, pitch = tp.pitch();
   const bool pair_store = C == 1 && (W & 1) == 0 && x + 2 <= W;
   int xo[2], x1[2], tb[2];
   double m0x1[2], m3x1[2], m6x1[2], dxo[2];
@@ -1237,7 +928,7 @@ __device__ __forceinline__ void persp_rows(const uint16_t* stile, const Box& box
     const int xc = min(x + q, W - 1);  // columns past the edge reuse the last column's taps
     xo[q] = xc - xc % bw0;
     x1[q] = xc - xo[q];
-    tb[q] = (xo[q] - xb) >> 6;  // TAB (bw0 == 64): the pixel's block of the tile (0 or 1)
+    tb[q] = (xo[q] - t.xb) >> 6;  // TAB (bw0 == 64): the pixel's block of the tile (0 or 1)
     // row-invariant: the column products and the block origin (round 3: hoisted out of
     // the row loop, and X0 / Y0 / W0 evaluated once per row for the lane's pixel pair)
     m0x1[q] = M[0] * x1[q];
@@ -1251,13 +942,13 @@ __device__ __forceinline__ void persp_rows(const uint16_t* stile, const Box& box
   // coordinates shifted by 11 (bits 16+: the pixel, bits 11-15: the 1/32 fraction) and the
   // LDS byte offset as one v_dot2 with (2, 2 pitch) -- as fast_rows (the generic form costs a
   // quarter-rate v_mul_lo_u32 and two more subtractions per tap)
-  const double cx = 0x1.8p52 - 32.0 * box.ax0, cy = 0x1.8p52 - 32.0 * box.sy0;
+  const double cx = 0x1.8p52 - 32.0 * tp.ax0, cy = 0x1.8p52 - 32.0 * tp.sy0;
   typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-  const u16x2 pitch2 = {(unsigned short)2, (unsigned short)(2 * box.pitch)};
+  const u16x2 pitch2 = {(unsigned short)2, (unsigned short)(2 * pitch)};
   const char* sbytes = reinterpret_cast<const char*>(stile);
 #pragma unroll
   for (int i = 0; i < Cfg::kTileH / 4; ++i) {
-    const int y = yb + wave + 4 * i;  // wave-uniform
+    const int y = t.yb + t.wave + 4 * i;  // wave-uniform
     if (y >= H) break;
     uint16_t o[2 * C];
     const double dy = (double)y;
@@ -1265,7 +956,7 @@ __device__ __forceinline__ void persp_rows(const uint16_t* stile, const Box& box
     if (TAB) {  // the workgroup's table (same expressions, evaluated once per (row, block))
 #pragma unroll
       for (int p = 0; p < 2; ++p) {
-        const double* e = ptab + 3 * (2 * (wave + 4 * i) + tb[p]);
+        const double* e = ptab + 3 * (2 * (t.wave + 4 * i) + tb[p]);
         X0[p] = e[0];
         Y0[p] = e[1];
         W0[p] = e[2];
@@ -1291,9 +982,9 @@ __device__ __forceinline__ void persp_rows(const uint16_t* stile, const Box& box
         const uint32_t tX = X << 11, tY = Y << 11;
         const uint32_t cr = __builtin_amdgcn_perm(tY, tX, 0x07060302u);  // (column, row) as u16 x 2
         const uint32_t off = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, cr), pitch2, 0u, false);
-        const uint16_t* t = reinterpret_cast<const uint16_t*>(sbytes + off);
+        const uint16_t* tp0 = reinterpret_cast<const uint16_t*>(sbytes + off);
         const uint32_t fx = X & 31, fy = Y & 31;
-        const uint32_t v00 = t[0], v01 = t[1], v10 = t[box.pitch], v11 = t[box.pitch + 1];
+        const uint32_t v00 = tp0[0], v01 = tp0[1], v10 = tp0[pitch], v11 = tp0[pitch + 1];
         if constexpr (DARK) {
           const uint32_t ax = 32 - fx, ay = 32 - fy;
           uint32_t h0 = __umul24(v00, ax) + __umul24(v01, fx);
@@ -1309,10 +1000,10 @@ __device__ __forceinline__ void persp_rows(const uint16_t* stile, const Box& box
       persp_px<MODE == 0>(X0[p], Y0[p], W0[p], m0x1[p], m3x1[p], m6x1[p], X, Y);
       if (MODE == 0) {
         const int fx = X & 31, fy = Y & 31;
-        const int li = (int)__umul24((uint32_t)((Y >> 5) - box.sy0), (uint32_t)box.pitch) + ((X >> 5) - box.ax0);
+        const int li = (int)__umul24((uint32_t)((Y >> 5) - tp.sy0), (uint32_t)pitch) + ((X >> 5) - tp.ax0);
 #pragma unroll
         for (int k = 0; k < C; ++k) {
-          const int i00 = li * C + k, i10 = i00 + box.pitch * C;
+          const int i00 = li * C + k, i10 = i00 + pitch * C;
           o[p * C + k] = blend_exact(tap(stile, i00), tap(stile, i00 + C), tap(stile, i10), tap(stile, i10 + C), fx, fy);
         }
       } else if (MODE == 1) {
@@ -1347,78 +1038,62 @@ __global__ __launch_bounds__(kThreads) __attribute__((target("no-unaligned-acces
 warp_perspective_u16_kernel(const uint16_t* __restrict__ src, uint16_t* __restrict__ dst,
                             const TilePlan* __restrict__ plan, const double* __restrict__ minv, int H, int W, int bw0) {
   __shared__ __attribute__((aligned(16))) uint16_t stile[Cfg::kLdsElems];
-  const int ntx = gridDim.x, nty = gridDim.y;
-  const int tile = xcd_remap(blockIdx.x + ntx * (blockIdx.y + nty * blockIdx.z), ntx * nty * gridDim.z);
-  const int f = tile / (ntx * nty);
-  const int t2 = tile - f * ntx * nty;
-  const int xb = (t2 % ntx) * kTileW, yb = (t2 / ntx) * Cfg::kTileH;
+  const TileId t = tile_decode<Cfg::kTileH>();
   const int tid = threadIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-  const uint16_t* S = src + (size_t)f * H * W * C;
-  uint16_t* Dst = dst + (size_t)f * H * W * C;
+  const uint16_t* S = src + (size_t)t.f * H * W * C;
+  uint16_t* Dst = dst + (size_t)t.f * H * W * C;
 
-  const Box box = unpack(plan[tile]);
+  const TilePlan tp = plan[t.tile];
   KCMC_LDS_SENTINEL(stile, Cfg::kLdsElems, tid);
-  const bool vec_stage = (C == 1) && ((W & 7) == 0);
-  uint4 chunk[Cfg::kRowPasses];
-  uint4 cchunk[C > 1 ? VecC<Cfg, C>::kPasses : 1];
-  if (box.mode == 0 && vec_stage) stage_issue<Cfg>(S, box, H, W, tid, chunk);
-  if constexpr (C > 1) {
-    if (box.mode == 0 && (W & 7) == 0) stage_vec_c_issue<Cfg, C>(S, box, H, W, tid, cchunk);
-  }
+  BoxLoads<Cfg, C> loads;
+  box_issue<Cfg, C>(S, tp, H, W, loads);
   double M[9];
 #pragma unroll
-  for (int k = 0; k < 9; ++k) M[k] = minv[9 * (size_t)f + k];
+  for (int k = 0; k < 9; ++k) M[k] = minv[9 * (size_t)t.f + k];
   double* ptab = reinterpret_cast<double*>(stile + PerspTab<Cfg>::kBoxElems);
-  const bool tab = bw0 == 64 && box.mode != 1;  // uniform
+  const bool tab = bw0 == 64 && tp.mode != 1;  // uniform
   if (tab) {
     for (int e = tid; e < PerspTab<Cfg>::kEntries; e += kThreads) {
-      const double dy = (double)(yb + (e >> 1)), dxo = (double)(xb + 64 * (e & 1));
+      const double dy = (double)(t.yb + (e >> 1)), dxo = (double)(t.xb + 64 * (e & 1));
       ptab[3 * e] = M[0] * dxo + M[1] * dy + M[2];
       ptab[3 * e + 1] = M[3] * dxo + M[4] * dy + M[5];
       ptab[3 * e + 2] = M[6] * dxo + M[7] * dy + M[8];
     }
   }
+  const bool count = C == 1 && (W & 7) == 0;  // one channel, 16-byte staging
   uint32_t* flags = reinterpret_cast<uint32_t*>(stile) + PerspTab<Cfg>::kFlagWord;
-  if (box.mode == 0) {
-    if (vec_stage) {
-      stage_land<Cfg>(stile, box, tid, chunk);
-      // bright (>= 16384) staged chunks of the box, counted per wave into the flag words
+  if (tp.mode == 0) {
+    box_land<Cfg, C>(stile, S, tp, H, W, loads);
+    if (count) {  // the box's bright (>= 16384) chunks, counted per wave into the flag words
       uint32_t nb = 0;
 #pragma unroll
-      for (int k = 0; k < Cfg::kRowPasses; ++k)
-        nb += __builtin_popcountll(
-            __builtin_amdgcn_ballot_w64(((chunk[k].x | chunk[k].y | chunk[k].z | chunk[k].w) & 0xc000c000u) != 0));
-      if (lane == 0) flags[wave] = nb;
-    } else if (C > 1 && (W & 7) == 0) {
-      if constexpr (C > 1) stage_vec_c_land<Cfg, C>(stile, box, tid, cchunk);
-    } else
-      stage_scalar<C>(S, stile, box, H, W, tid);
+      for (int k = 0; k < BoxLoads<Cfg, C>::kPasses; ++k) nb += bright_chunks(loads.chunk[k]);
+      if (t.lane == 0) flags[t.wave] = nb;
+    }
   }
   __syncthreads();
-  if (box.mode == 1)
-    persp_rows<Cfg, C, 1, false>(stile, box, S, Dst, M, H, W, xb, yb, wave, lane, bw0, ptab);
+  if (tp.mode == 1)
+    persp_rows<Cfg, C, 1, false>(stile, tp, S, Dst, M, H, W, t, bw0, ptab);
   else if (tab) {
-    if (box.mode == 0) {
+    if (tp.mode == 0) {
       const uint4 fl = *reinterpret_cast<const uint4*>(flags);
-      if (vec_stage && fl.x + fl.y + fl.z + fl.w == 0)
-        persp_rows<Cfg, C, 0, true, true>(stile, box, S, Dst, M, H, W, xb, yb, wave, lane, bw0, ptab);
+      if (count && fl.x + fl.y + fl.z + fl.w == 0)
+        persp_rows<Cfg, C, 0, true, true>(stile, tp, S, Dst, M, H, W, t, bw0, ptab);
       else
-        persp_rows<Cfg, C, 0, true>(stile, box, S, Dst, M, H, W, xb, yb, wave, lane, bw0, ptab);
+        persp_rows<Cfg, C, 0, true>(stile, tp, S, Dst, M, H, W, t, bw0, ptab);
     } else
-      persp_rows<Cfg, C, 2, true>(stile, box, S, Dst, M, H, W, xb, yb, wave, lane, bw0, ptab);
-  } else if (box.mode == 0) {
-    persp_rows<Cfg, C, 0, false>(stile, box, S, Dst, M, H, W, xb, yb, wave, lane, bw0, ptab);
+      persp_rows<Cfg, C, 2, true>(stile, tp, S, Dst, M, H, W, t, bw0, ptab);
+  } else if (tp.mode == 0) {
+    persp_rows<Cfg, C, 0, false>(stile, tp, S, Dst, M, H, W, t, bw0, ptab);
   } else {
-    persp_rows<Cfg, C, 2, false>(stile, box, S, Dst, M, H, W, xb, yb, wave, lane, bw0, ptab);
+    persp_rows<Cfg, C, 2, false>(stile, tp, S, Dst, M, H, W, t, bw0, ptab);
   }
 }
 
-template <class Cfg>
-size_t persp_workspace_bytes(int n_frames, int H, int W) {
-  const size_t tiles = (size_t)ceil_div(W, kTileW) * ceil_div(H, Cfg::kTileH) * n_frames;
-  return tiles * sizeof(TilePlan) + (size_t)n_frames * 9 * sizeof(double);
-}
+// ------------------------------------------------------------------------- host
+// Row-origin table entries per (frame, y & 3): padded so that a wave's scalar loads of
+// its kTileH / 4 entries stay inside the frame's block.
+inline int rowtab_hq(int H) { return ceil_div(H, 4) + 16; }
 
 // WarpPerspectiveInvoker's block width: bh0 = min(16, H), bw0 = min(1024 / bh0, W)
 inline int persp_bw0(int H, int W) {
@@ -1426,92 +1101,105 @@ inline int persp_bw0(int H, int W) {
   return 1024 / bh0 < W ? 1024 / bh0 : W;
 }
 
-// Workspace layout of the perspective warp: minv [F, 9] f64, plan [tiles].
-template <int C, class Cfg = typename CfgFor<C>::type>
-void launch_persp_plan(const double* M, int n_frames, int H, int W, int inverse_map, void* ws, hipStream_t s) {
-  const int ntx = ceil_div(W, kTileW), nty = ceil_div(H, Cfg::kTileH);
-  const long long tiles = (long long)ntx * nty * n_frames;
-  double* minv = static_cast<double*>(ws);
-  TilePlan* plan = reinterpret_cast<TilePlan*>(minv + 9 * (size_t)n_frames);
-  hipLaunchKernelGGL((persp_plan_kernel<C, Cfg>), dim3((unsigned)((tiles + 255) / 256)), dim3(256), 0, s, M, n_frames,
-                     H, W, inverse_map, ntx, nty, plan, minv);
-}
-
-template <int C, class Cfg = typename CfgFor<C>::type>
-void launch_persp_tiles(const uint16_t* src, uint16_t* dst, int n_frames, int H, int W, const void* ws, hipStream_t s) {
-  const int ntx = ceil_div(W, kTileW), nty = ceil_div(H, Cfg::kTileH);
-  const double* minv = static_cast<const double*>(ws);
-  const TilePlan* plan = reinterpret_cast<const TilePlan*>(minv + 9 * (size_t)n_frames);
-  hipLaunchKernelGGL((warp_perspective_u16_kernel<C, Cfg>), dim3(ntx, nty, n_frames), dim3(kThreads), 0, s, src, dst,
-                     plan, minv, H, W, persp_bw0(H, W));
-}
-
-template <int C, class Cfg = typename CfgFor<C>::type>
-void launch_persp(const uint16_t* src, uint16_t* dst, const double* M, int n_frames, int H, int W, int inverse_map,
-                  void* ws, hipStream_t s) {
-  launch_persp_plan<C, Cfg>(M, n_frames, H, W, inverse_map, ws, s);
-  launch_persp_tiles<C, Cfg>(src, dst, n_frames, H, W, ws, s);
-}
-
-// The plan workspace of one warp call (both launch forms use the same layout).
-size_t plan_bytes(int n_frames, int H, int W, int C, bool perspective) {
-  if (perspective)
-    return C == 1 ? persp_workspace_bytes<BlockCfg>(n_frames, H, W) : persp_workspace_bytes<ChanCfg>(n_frames, H, W);
-  if (C == 1) return use_tile64(H) ? warp_workspace_bytes<Block64Cfg>(n_frames, H, W)
-                                   : warp_workspace_bytes<BlockCfg>(n_frames, H, W);
-  return warp_workspace_bytes<ChanCfg>(n_frames, H, W);
-}
-
-// The plan / tile launches of a warp call; `tiles` false: the plan, true: the tiles.
-void launch_part(bool tiles, bool perspective, const uint16_t* src, uint16_t* dst, const double* M, int n_frames,
-                 int H, int W, int C, int inverse_map, void* ws, hipStream_t s) {
-  if (perspective) {
-    switch (C) {
-      case 1:
-        tiles ? launch_persp_tiles<1>(src, dst, n_frames, H, W, ws, s)
-              : launch_persp_plan<1>(M, n_frames, H, W, inverse_map, ws, s);
-        break;
-      case 3:
-        tiles ? launch_persp_tiles<3>(src, dst, n_frames, H, W, ws, s)
-              : launch_persp_plan<3>(M, n_frames, H, W, inverse_map, ws, s);
-        break;
-      default:
-        tiles ? launch_persp_tiles<4>(src, dst, n_frames, H, W, ws, s)
-              : launch_persp_plan<4>(M, n_frames, H, W, inverse_map, ws, s);
-        break;
-    }
-    return;
+// Tile grid and workspace layout of both warps: minv [F, n] f64 (n = 6 doubles per affine
+// map, 9 per homography), rowtab [F, 4, hq] int2 (hq = 0: no row table, the perspective
+// warp), plan [tiles].
+template <class Cfg>
+struct LinearWs {
+  int ntx, nty, hq;
+  long long tiles;
+  size_t tab_at, plan_at, bytes;  // byte offsets of rowtab and plan, and the whole
+  LinearWs(bool perspective, int n_frames, int H, int W) {
+    ntx = ceil_div(W, kTileW), nty = ceil_div(H, Cfg::kTileH);
+    tiles = (long long)ntx * nty * n_frames;
+    hq = perspective ? 0 : rowtab_hq(H);
+    tab_at = (size_t)n_frames * (perspective ? 9 : 6) * sizeof(double);
+    plan_at = tab_at + (size_t)n_frames * 4 * hq * sizeof(int2);
+    bytes = plan_at + (size_t)tiles * sizeof(TilePlan);
   }
-  switch (C) {
-    case 1:
-      if (use_tile64(H))
-        tiles ? launch_warp_tiles<1, Block64Cfg>(src, dst, n_frames, H, W, ws, s)
-              : launch_warp_plan<1, Block64Cfg>(M, n_frames, H, W, inverse_map, ws, s);
-      else
-        tiles ? launch_warp_tiles<1>(src, dst, n_frames, H, W, ws, s)
-              : launch_warp_plan<1>(M, n_frames, H, W, inverse_map, ws, s);
-      break;
-    case 3:
-      tiles ? launch_warp_tiles<3>(src, dst, n_frames, H, W, ws, s)
-            : launch_warp_plan<3>(M, n_frames, H, W, inverse_map, ws, s);
-      break;
-    default:
-      tiles ? launch_warp_tiles<4>(src, dst, n_frames, H, W, ws, s)
-            : launch_warp_plan<4>(M, n_frames, H, W, inverse_map, ws, s);
-      break;
+  double* minv(void* ws) const { return static_cast<double*>(ws); }
+  int2* rowtab(void* ws) const { return reinterpret_cast<int2*>(static_cast<char*>(ws) + tab_at); }
+  TilePlan* plan(void* ws) const { return reinterpret_cast<TilePlan*>(static_cast<char*>(ws) + plan_at); }
+};
+
+template <class Cfg>
+size_t warp_workspace_bytes(int n_frames, int H, int W) {
+  return LinearWs<Cfg>(false, n_frames, H, W).bytes;
+}
+
+// Plan + tile launches of either warp on `s`; ws holds LinearWs<Cfg>::bytes bytes.
+template <bool PERSP, int C, class Cfg>
+void launch_linear(const uint16_t* src, uint16_t* dst, const double* M, int n_frames, int H, int W, int inverse_map,
+                   void* ws, hipStream_t s) {
+  const LinearWs<Cfg> w(PERSP, n_frames, H, W);
+  const dim3 plan_grid((unsigned)((w.tiles + 255) / 256)), tile_grid(w.ntx, w.nty, n_frames);
+  if constexpr (PERSP) {
+    hipLaunchKernelGGL((persp_plan_kernel<C, Cfg>), plan_grid, dim3(256), 0, s, M, n_frames, H, W, inverse_map, w.ntx,
+                       w.nty, w.plan(ws), w.minv(ws));
+    hipLaunchKernelGGL((warp_perspective_u16_kernel<C, Cfg>), tile_grid, dim3(kThreads), 0, s, src, dst, w.plan(ws),
+                       w.minv(ws), H, W, persp_bw0(H, W));
+  } else {
+    hipLaunchKernelGGL((warp_plan_kernel<C, Cfg>), plan_grid, dim3(256), 0, s, M, n_frames, H, W, inverse_map, w.ntx,
+                       w.nty, w.plan(ws), w.minv(ws), w.rowtab(ws), w.hq);
+    hipLaunchKernelGGL((warp_affine_u16_kernel<C, Cfg>), tile_grid, dim3(kThreads), 0, s, src, dst, w.plan(ws),
+                       w.minv(ws), w.rowtab(ws), w.hq, H, W);
   }
 }
 
-// The argument checks shared by every warp entry point.
-int check_warp_args(const char* who, int n_frames, int H, int W, int C) {
-  const std::string w(who);
+// The affine warp; ws holds warp_workspace_bytes<Cfg>(n_frames, H, W) bytes.
+template <int C, class Cfg = typename CfgFor<C>::type>
+void launch_warp(const uint16_t* src, uint16_t* dst, const double* M, int n_frames, int H, int W, int inverse_map,
+                 void* ws, hipStream_t s) {
+  launch_linear<false, C, Cfg>(src, dst, M, n_frames, H, W, inverse_map, ws, s);
+}
+
+// (perspective, C, use_tile64(H)) -> f(perspective, C and the configuration as types)
+template <bool PERSP, int C, class Cfg>
+struct LinearCfg {
+  static constexpr bool kPersp = PERSP;
+  static constexpr int kC = C;
+  using cfg = Cfg;
+};
+
+template <bool PERSP, typename F>
+int with_linear_cfg(int C, int H, F f) {
+  if constexpr (!PERSP)
+    if (C == 1 && use_tile64(H)) return f(LinearCfg<PERSP, 1, Block64Cfg>());
+  if (C == 1) return f(LinearCfg<PERSP, 1, BlockCfg>());
+  return C == 3 ? f(LinearCfg<PERSP, 3, ChanCfg>()) : f(LinearCfg<PERSP, 4, ChanCfg>());
+}
+
+template <typename F>
+int with_linear_cfg(bool perspective, int C, int H, F f) {
+  return perspective ? with_linear_cfg<true>(C, H, f) : with_linear_cfg<false>(C, H, f);
+}
+
+// The body of both entries.
+int run_linear_warp(const char* name, const char* kernel_name, bool perspective, kcmc_ctx* ctx, const uint16_t* src,
+                    uint16_t* dst, const double* M, int n_frames, int H, int W, int C, int inverse_map,
+                    kcmc_stream_t stream) {
+  const std::string w(name);
+  if (!ctx) return fail(KCMC_EINVAL, w + ": ctx is NULL");
   if (n_frames < 0 || H < 0 || W < 0) return fail(KCMC_EINVAL, w + ": negative size");
   if (H > 32767 || W > 32767) return fail(KCMC_EUNSUPPORTED, w + ": H, W must be < 32768");
   if (n_frames > 65535) return fail(KCMC_EUNSUPPORTED, w + ": at most 65535 frames per call");
   if (C != 1 && C != 3 && C != 4) return fail(KCMC_EUNSUPPORTED, w + ": C must be 1, 3 or 4");
   if ((long long)ceil_div(W, kTileW) * ceil_div(H, ChanCfg::kTileH) * n_frames >= (1ll << 31))
     return fail(KCMC_EUNSUPPORTED, w + ": too many tiles in one call");
-  return KCMC_OK;
+  if (n_frames == 0 || H == 0 || W == 0) return KCMC_OK;
+  if (!src || !dst || !M) return fail(KCMC_EINVAL, w + ": NULL pointer");
+  if (src == dst) return fail(KCMC_EINVAL, w + ": in-place warp is not supported");
+  hipStream_t s = (hipStream_t)stream;
+  return with_linear_cfg(perspective, C, H, [&](auto k) -> int {
+    using K = decltype(k);
+    void* ws = nullptr;
+    const size_t wsb = LinearWs<typename K::cfg>(K::kPersp, n_frames, H, W).bytes;
+    KCMC_TRY(workspace_alloc(ctx, &ws, wsb, s));
+    launch_linear<K::kPersp, K::kC, typename K::cfg>(src, dst, M, n_frames, H, W, inverse_map, ws, s);
+    const int rc = launch_check(kernel_name);
+    KCMC_TRY(workspace_free(ctx, ws, s, wsb));
+    return rc;
+  });
 }
 
 }  // namespace
@@ -1521,36 +1209,12 @@ using namespace kcmc;
 
 extern "C" int kcmc_warp_perspective_u16(kcmc_ctx* ctx, const uint16_t* src, uint16_t* dst, const double* M,
                                          int n_frames, int H, int W, int C, int inverse_map, kcmc_stream_t stream) {
-  if (!ctx) return fail(KCMC_EINVAL, "kcmc_warp_perspective_u16: ctx is NULL");
-  KCMC_TRY(check_warp_args("kcmc_warp_perspective_u16", n_frames, H, W, C));
-  if (n_frames == 0 || H == 0 || W == 0) return KCMC_OK;
-  if (!src || !dst || !M) return fail(KCMC_EINVAL, "kcmc_warp_perspective_u16: NULL pointer");
-  if (src == dst) return fail(KCMC_EINVAL, "kcmc_warp_perspective_u16: in-place warp is not supported");
-  hipStream_t s = (hipStream_t)stream;
-  void* ws = nullptr;
-  const size_t wsb = plan_bytes(n_frames, H, W, C, true);
-  KCMC_TRY(workspace_alloc(ctx, &ws, wsb, s));
-  launch_part(false, true, src, dst, M, n_frames, H, W, C, inverse_map, ws, s);
-  launch_part(true, true, src, dst, M, n_frames, H, W, C, inverse_map, ws, s);
-  const int rc = launch_check("warp_perspective_u16_kernel");
-  KCMC_TRY(workspace_free(ctx, ws, s, wsb));
-  return rc;
+  return run_linear_warp("kcmc_warp_perspective_u16", "warp_perspective_u16_kernel", true, ctx, src, dst, M, n_frames,
+                         H, W, C, inverse_map, stream);
 }
 
 extern "C" int kcmc_warp_affine_u16(kcmc_ctx* ctx, const uint16_t* src, uint16_t* dst, const double* M,
                                     int n_frames, int H, int W, int C, int inverse_map, kcmc_stream_t stream) {
-  if (!ctx) return fail(KCMC_EINVAL, "kcmc_warp_affine_u16: ctx is NULL");
-  KCMC_TRY(check_warp_args("kcmc_warp_affine_u16", n_frames, H, W, C));
-  if (n_frames == 0 || H == 0 || W == 0) return KCMC_OK;
-  if (!src || !dst || !M) return fail(KCMC_EINVAL, "kcmc_warp_affine_u16: NULL pointer");
-  if (src == dst) return fail(KCMC_EINVAL, "kcmc_warp_affine_u16: in-place warp is not supported");
-  hipStream_t s = (hipStream_t)stream;
-  void* ws = nullptr;
-  const size_t wsb = plan_bytes(n_frames, H, W, C, false);
-  KCMC_TRY(workspace_alloc(ctx, &ws, wsb, s));
-  launch_part(false, false, src, dst, M, n_frames, H, W, C, inverse_map, ws, s);
-  launch_part(true, false, src, dst, M, n_frames, H, W, C, inverse_map, ws, s);
-  const int rc = launch_check("warp_affine_u16_kernel");
-  KCMC_TRY(workspace_free(ctx, ws, s, wsb));
-  return rc;
+  return run_linear_warp("kcmc_warp_affine_u16", "warp_affine_u16_kernel", false, ctx, src, dst, M, n_frames, H, W, C,
+                         inverse_map, stream);
 }

@@ -1,10 +1,12 @@
-// The tile skeleton the grayscale box-staging warps share (warp_cubic.hip K3c, warp_field.hip
-// K3f; the bilinear warp.hip keeps its own plan and staging): everything here is described once.
+// The tile skeleton the four box-staging warps share (warp.hip K3 / K3p, warp_cubic.hip K3c,
+// warp_field.hip K3f): everything here is described once.  The bilinear warp.hip adds its own
+// configurations (tile height, budget and passes per channel count), its own classification
+// (the budget depends on them), a fixed-pitch fast path (mode 3) and interleaved staging.
 //
 // Layout: 128 x 56 output tiles (64 rows under use_tile64), one workgroup of 256 threads per tile,
 // one output row per wave and pass, lane l the pixels 2l, 2l + 1.  A plan kernel (one thread per
 // tile) inverts the map and bounds the tile's source box: the affine part is separable and
-// monotone (warp.hip source_box), so affine_box takes it at the tile's corner rows / columns, and
+// monotone (affine_box), so it is taken at the tile's corner rows / columns, and
 // the kernel widens it to its footprint.  classify_box sorts the tile: a box within the staging
 // budget (pitch <= 256, rows <= 72, 20 KB) is staged in LDS with zeros outside the image
 // (BORDER_CONSTANT), a box that misses the image stores zeros, every other tile gathers from
@@ -34,11 +36,12 @@ constexpr int kMaxPitch = 256;    // staged row length limit (32 x 16-byte chunk
 constexpr int kLdsElems = 10240;  // uint16 staging budget per box (20 KB)
 constexpr int kRowPasses = 9;     // staging passes of 8 rows x 32 chunks (box rows <= 72)
 
-// the affine warp's tile-height rule (warp.hip use_tile64)
+// the one-channel tile-height rule: frame heights that are a multiple of 64 but not of 56 (512)
+// lose 9 % of their tiles to a partial last tile row at 56 rows
 inline bool use_tile64(int H) { return H % 64 == 0 && H % 56 != 0; }
 
 struct TilePlan {
-  int mode;        // 0: staged in LDS, 1: zeros, 2: direct gather
+  int mode;        // 0: staged in LDS, 1: zeros, 2: direct gather, 3: fixed-pitch fast path (warp.hip)
   int ax0, sy0;    // first staged column (multiple of 8) / row
   int pitch_rows;  // pitch | rows << 16 | (box inside the image) << 31
   __device__ int pitch() const { return pitch_rows & 0xffff; }
@@ -125,15 +128,16 @@ __device__ __forceinline__ TileId tile_decode() {
 }
 
 // Staging, first half: thread tid loads chunk c = tid & 31 of box rows tid >> 5 + 8 k (zeros
-// where the chunk lies outside the box or the image).
+// where the chunk lies outside the box or the image), k < PASSES (deduced: box rows <= 8 PASSES).
+template <int PASSES>
 __device__ __forceinline__ void stage_load(const uint16_t* S, const TilePlan& tp, int H, int W,
-                                           bool vec_stage, uint4 (&chunk)[kRowPasses]) {
+                                           bool vec_stage, uint4 (&chunk)[PASSES]) {
   const int tid = threadIdx.x, cpr = tp.pitch() >> 3, sc = tid & 31, sr = tid >> 5;
   if (vec_stage) {
     const int cx = tp.ax0 + 8 * sc;
     const bool col_ok = sc < cpr && cx >= 0 && cx < W;
 #pragma unroll
-    for (int k = 0; k < kRowPasses; ++k) {
+    for (int k = 0; k < PASSES; ++k) {
       const int r = sr + 8 * k, cy = tp.sy0 + r;
       chunk[k] = make_uint4(0u, 0u, 0u, 0u);
       if (r < tp.rows() && col_ok && (unsigned)cy < (unsigned)H)
@@ -142,24 +146,33 @@ __device__ __forceinline__ void stage_load(const uint16_t* S, const TilePlan& tp
   }
 }
 
-// Second half: the chunks into LDS, or (W % 8 != 0 or an unaligned slab) the box element by
-// element.  stile holds kLdsElems elements at least.
+// Element-wise staging of a C-channel box (W % 8 != 0 or an unaligned slab).
+template <int C>
+__device__ __forceinline__ void stage_elements(uint16_t* stile, const uint16_t* S, const TilePlan& tp, int H, int W) {
+  const int rowe = tp.pitch() * C;
+  for (int q = threadIdx.x; q < tp.rows() * rowe; q += kThreads) {
+    const int r = q / rowe, e = q - r * rowe;
+    const int cy = tp.sy0 + r, cx = tp.ax0 + e / C, k = e % C;
+    stile[q] = ((unsigned)cy < (unsigned)H && (unsigned)cx < (unsigned)W) ? S[((size_t)cy * W + cx) * C + k]
+                                                                          : (uint16_t)0;
+  }
+}
+
+// Second half: the chunks into LDS, or the box element by element.  stile holds the box's
+// pitch * rows elements at least.
+template <int PASSES>
 __device__ __forceinline__ void stage_commit(uint16_t* stile, const uint16_t* S, const TilePlan& tp, int H,
-                                             int W, bool vec_stage, const uint4 (&chunk)[kRowPasses]) {
+                                             int W, bool vec_stage, const uint4 (&chunk)[PASSES]) {
   const int pitch = tp.pitch(), rows = tp.rows();
   const int tid = threadIdx.x, cpr = pitch >> 3, sc = tid & 31, sr = tid >> 5;
   if (vec_stage) {
 #pragma unroll
-    for (int k = 0; k < kRowPasses; ++k) {
+    for (int k = 0; k < PASSES; ++k) {
       const int r = sr + 8 * k;
       if (r < rows && sc < cpr) *reinterpret_cast<uint4*>(&stile[r * pitch + 8 * sc]) = chunk[k];
     }
   } else if (tp.mode == 0) {
-    for (int q = tid; q < rows * pitch; q += kThreads) {
-      const int r = q / pitch, e = q - r * pitch;
-      const int cy = tp.sy0 + r, cx = tp.ax0 + e;
-      stile[q] = ((unsigned)cy < (unsigned)H && (unsigned)cx < (unsigned)W) ? S[(size_t)cy * W + cx] : (uint16_t)0;
-    }
+    stage_elements<1>(stile, S, tp, H, W);
   }
 }
 

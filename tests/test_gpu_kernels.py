@@ -341,9 +341,12 @@ def test_ransac_gather_mode_matches_contiguous(dev):
 
 
 # ------------------------------------------------------------------------ K3
-@pytest.mark.parametrize("shape", [(1, 5, 7), (3, 64, 128), (2, 67, 131), (2, 130, 257), (2, 90, 200), (1, 57, 136),
-                                   (1, 1080, 1920)])
-def test_warp_matches_oracle(dev, shape):
+WARP_SHAPES = [(1, 5, 7), (3, 64, 128), (2, 67, 131), (2, 130, 257), (2, 90, 200), (1, 57, 136), (1, 1080, 1920)]
+
+
+def warp_case(shape):
+    """(frames, forward maps) of test_warp_matches_oracle (also classified on the host by
+    test_warp_linear_host.py)."""
     F, H, W = shape
     rng = np.random.default_rng(H * W)
     imgs = rng.integers(0, 65536, shape).astype(np.uint16)
@@ -353,7 +356,13 @@ def test_warp_matches_oracle(dev, shape):
         if f % 3 == 1:
             A[:, :2] *= 1.05
         Ms.append(A)
-    Ms = np.stack(Ms)
+    return imgs, np.stack(Ms)
+
+
+@pytest.mark.parametrize("shape", WARP_SHAPES)
+def test_warp_matches_oracle(dev, shape):
+    F = shape[0]
+    imgs, Ms = warp_case(shape)
     out = stages.warp_affine_u16(_t(imgs, dev), _t(Ms, dev)).cpu().numpy()
     for f in range(F):
         assert np.array_equal(out[f], oracle.warp_affine_u16(imgs[f], Ms[f])), f
@@ -491,36 +500,43 @@ def test_warp_multichannel_fast_path_value_ranges(dev, C, shape, values):
         assert np.array_equal(out[f], oracle.warp_affine_u16(imgs[f], Ms[f])), f
 
 
-@pytest.mark.parametrize("C", [3, 4])
-def test_warp_multichannel(dev, C):
+def multichannel_case(C):
     rng = np.random.default_rng(C)
     imgs = rng.integers(0, 65536, (2, 50, 70, C)).astype(np.uint16)
-    Ms = np.stack([synthetic.rigid(0.02, 1.5, -2.25), synthetic.rigid(-0.01, -3.3, 0.7)])
+    return imgs, np.stack([synthetic.rigid(0.02, 1.5, -2.25), synthetic.rigid(-0.01, -3.3, 0.7)])
+
+
+@pytest.mark.parametrize("C", [3, 4])
+def test_warp_multichannel(dev, C):
+    imgs, Ms = multichannel_case(C)
     out = stages.warp_affine_u16(_t(imgs, dev), _t(Ms, dev)).cpu().numpy()
     for f in range(2):
         assert np.array_equal(out[f], oracle.warp_affine_u16(imgs[f], Ms[f]))
 
 
-def test_warp_all_tile_paths_at_1080p(dev):
-    """Rotations/zooms that put tiles on every path: LDS-staged boxes, boxes too large
-    for LDS (direct gather), and boxes entirely outside the frame (zeros)."""
+def all_tile_paths_case():
     rng = np.random.default_rng(41)
     H, W = 1080, 1920
     img = rng.integers(0, 65536, (H, W)).astype(np.uint16)
     Ms = [synthetic.rigid(np.deg2rad(6.0), 10.5, -7.25), synthetic.rigid(np.deg2rad(-30.0), 300, 100),
           np.array([[0.6, 0.01, 5.0], [-0.01, 0.6, 3.0]]), np.array([[1.8, 0.0, -400.0], [0.0, 1.8, -300.0]]),
           synthetic.rigid(0.0, 1500.0, 0.0)]
-    imgs = distinct_frames(img, len(Ms))
+    return distinct_frames(img, len(Ms)), Ms
+
+
+def test_warp_all_tile_paths_at_1080p(dev):
+    """Rotations/zooms that put tiles on every path: LDS-staged boxes, boxes too large
+    for LDS (direct gather), and boxes entirely outside the frame (zeros)."""
+    imgs, Ms = all_tile_paths_case()
     out = stages.warp_affine_u16(_t(imgs, dev), _t(np.stack(Ms), dev)).cpu().numpy()
     for f, M in enumerate(Ms):
         assert np.array_equal(out[f], oracle.warp_affine_u16(imgs[f], M)), f
 
 
-@pytest.mark.parametrize("values", ["full", "14bit", "hot"])
-def test_warp_64_row_tiles(dev, values):
-    """Frame heights that are multiples of 64 but not of 56 (512 x 512: BASELINE config 3)
-    take 64-row tiles: the fixed-pitch fast path for small rotations, the general staged
-    path / direct gather / zeros for larger rotations, zooms and shifts off the frame."""
+TILE64_VALUES = ["full", "14bit", "hot"]
+
+
+def tile64_case(values):
     rng = np.random.default_rng(64)
     H, W = 512, 512
     if values == "full":
@@ -535,7 +551,15 @@ def test_warp_64_row_tiles(dev, values):
           synthetic.rigid(np.deg2rad(6.0), 10.5, -7.25), synthetic.rigid(np.deg2rad(-30.0), 100, 50),
           np.array([[0.6, 0.01, 5.0], [-0.01, 0.6, 3.0]]), np.array([[1.02, 0.0, -3.0], [0.0, 0.98, 2.0]]),
           synthetic.rigid(0.0, 900.0, 0.0), synthetic.rigid(0.0, 0.0, 0.0)]
-    imgs = distinct_frames(img, len(Ms))
+    return distinct_frames(img, len(Ms)), Ms
+
+
+@pytest.mark.parametrize("values", TILE64_VALUES)
+def test_warp_64_row_tiles(dev, values):
+    """Frame heights that are multiples of 64 but not of 56 (512 x 512: BASELINE config 3)
+    take 64-row tiles: the fixed-pitch fast path for small rotations, the general staged
+    path / direct gather / zeros for larger rotations, zooms and shifts off the frame."""
+    imgs, Ms = tile64_case(values)
     out = stages.warp_affine_u16(_t(imgs, dev), _t(np.stack(Ms), dev)).cpu().numpy()
     for f, M in enumerate(Ms):
         assert np.array_equal(out[f], oracle.warp_affine_u16(imgs[f], M)), f
@@ -559,21 +583,31 @@ def test_warp_nan_map_gives_zeros(dev):
         assert out[0].any() and np.array_equal(out[0], out[2])
 
 
-@pytest.mark.parametrize("shape", [(3, 120, 256, 3), (2, 96, 136, 4), (1, 2160, 3840, 3)])
-def test_warp_multichannel_vector_staging(dev, shape):
-    """C = 3 / 4 with W % 8 == 0: 16-byte staging of interleaved rows into 128 x 24
-    tiles (and, at 4K, tiles on every path)."""
+VECTOR_STAGING_SHAPES = [(3, 120, 256, 3), (2, 96, 136, 4), (1, 2160, 3840, 3)]
+
+
+def vector_staging_case(shape):
+    """(frames, affine maps, homographies) of test_warp_multichannel_vector_staging."""
     rng = np.random.default_rng(shape[1])
     imgs = rng.integers(0, 65536, shape).astype(np.uint16)
     F = shape[0]
     Ms = [synthetic.rigid(np.deg2rad(0.4), 3.7, -2.2), synthetic.rigid(np.deg2rad(-25.0), 40.0, 10.0),
           np.array([[1.6, 0.02, -30.0], [0.01, 1.6, -20.0]])][:F]
     Ms = np.stack(Ms)
+    Hs = np.concatenate([Ms, np.tile([[[0.0, 0.0, 1.0]]], (F, 1, 1))], axis=1)
+    Hs[:, 2, :2] = [2e-5, -1e-5]
+    return imgs, Ms, Hs
+
+
+@pytest.mark.parametrize("shape", VECTOR_STAGING_SHAPES)
+def test_warp_multichannel_vector_staging(dev, shape):
+    """C = 3 / 4 with W % 8 == 0: 16-byte staging of interleaved rows into 128 x 24
+    tiles (and, at 4K, tiles on every path)."""
+    F = shape[0]
+    imgs, Ms, Hs = vector_staging_case(shape)
     out = stages.warp_affine_u16(_t(imgs, dev), _t(Ms, dev)).cpu().numpy()
     for f in range(F):
         assert np.array_equal(out[f], oracle.warp_affine_u16(imgs[f], Ms[f])), f
-    Hs = np.concatenate([Ms, np.tile([[[0.0, 0.0, 1.0]]], (F, 1, 1))], axis=1)
-    Hs[:, 2, :2] = [2e-5, -1e-5]
     outp = stages.warp_perspective_u16(_t(imgs, dev), _t(Hs, dev)).cpu().numpy()
     for f in range(F):
         assert np.array_equal(outp[f], oracle.warp_perspective_u16(imgs[f], Hs[f])), f

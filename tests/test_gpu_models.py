@@ -172,20 +172,28 @@ def _homographies(rng, F, H, W):
     return np.stack(Ms)
 
 
-@pytest.mark.parametrize("shape", [(1, 5, 7), (3, 64, 128), (2, 67, 131), (2, 130, 257), (1, 1080, 1920)])
-def test_warp_perspective_matches_oracle(dev, shape):
+PERSPECTIVE_SHAPES = [(1, 5, 7), (3, 64, 128), (2, 67, 131), (2, 130, 257), (1, 1080, 1920)]
+
+
+def perspective_case(shape):
+    """(frames, homographies) of test_warp_perspective_matches_oracle (also classified on the
+    host by test_warp_linear_host.py)."""
     F, H, W = shape
     rng = np.random.default_rng(H * W + 1)
     imgs = rng.integers(0, 65536, shape).astype(np.uint16)
-    Ms = _homographies(rng, F, H, W)
+    return imgs, _homographies(rng, F, H, W)
+
+
+@pytest.mark.parametrize("shape", PERSPECTIVE_SHAPES)
+def test_warp_perspective_matches_oracle(dev, shape):
+    F = shape[0]
+    imgs, Ms = perspective_case(shape)
     out = stages.warp_perspective_u16(_t(imgs, dev), _t(Ms, dev)).cpu().numpy()
     for f in range(F):
         assert np.array_equal(out[f], oracle.warp_perspective_u16(imgs[f], Ms[f])), f
 
 
-def test_warp_perspective_extreme_maps_and_inverse(dev):
-    """Horizon inside the frame (denominator changes sign -> direct gather), singular
-    map, strong zoom, frames far outside, and WARP_INVERSE_MAP."""
+def extreme_perspective_case():
     rng = np.random.default_rng(81)
     H, W = 200, 300
     img = rng.integers(0, 65536, (H, W)).astype(np.uint16)
@@ -193,6 +201,14 @@ def test_warp_perspective_extreme_maps_and_inverse(dev):
           np.zeros((3, 3)), np.array([[2.5, 0, -100], [0, 2.5, -80], [0, 0, 1.0]]),
           np.array([[1, 0, 5000], [0, 1, 0], [0, 0, 1.0]]),
           np.array([[0.9, 0.05, 3], [-0.04, 1.1, 2], [-2e-4, 1e-4, 1]])]
+    return img, Ms
+
+
+def test_warp_perspective_extreme_maps_and_inverse(dev):
+    """Horizon inside the frame (denominator changes sign -> direct gather), singular
+    map, strong zoom, frames far outside, and WARP_INVERSE_MAP."""
+    img, Ms = extreme_perspective_case()
+    H, W = img.shape
     imgs = np.broadcast_to(img, (len(Ms), H, W)).copy()
     for inv in (False, True):
         out = stages.warp_perspective_u16(_t(imgs, dev), _t(np.stack(Ms), dev), inverse_map=inv).cpu().numpy()
@@ -201,11 +217,15 @@ def test_warp_perspective_extreme_maps_and_inverse(dev):
     assert np.array_equal(out[0], img)
 
 
-@pytest.mark.parametrize("C", [3, 4])
-def test_warp_perspective_multichannel(dev, C):
+def perspective_multichannel_case(C):
     rng = np.random.default_rng(90 + C)
     imgs = rng.integers(0, 65536, (2, 60, 90, C)).astype(np.uint16)
-    Ms = _homographies(rng, 2, 60, 90)
+    return imgs, _homographies(rng, 2, 60, 90)
+
+
+@pytest.mark.parametrize("C", [3, 4])
+def test_warp_perspective_multichannel(dev, C):
+    imgs, Ms = perspective_multichannel_case(C)
     out = stages.warp_perspective_u16(_t(imgs, dev), _t(Ms, dev)).cpu().numpy()
     for f in range(2):
         assert np.array_equal(out[f], oracle.warp_perspective_u16(imgs[f], Ms[f]))

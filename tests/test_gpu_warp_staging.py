@@ -20,15 +20,15 @@ from kcmc_amd import stages, synthetic
 
 pytestmark = pytest.mark.gpu
 
-TILE_W, FAST_PITCH, FAST_ROWS = 128, 144, 71  # warp.hip kTileW, kFastPitch, Fast<Cfg>::kRows
-MAX_PITCH, LDS_ELEMS, MAX_ROWS = 256, 10240, 72  # kMaxPitch, BlockCfg: kLdsElems, 8 * kRowPasses
+TILE_W, FAST_PITCH, FAST_ROWS = 128, 144, 71  # warp_tile.h kTileW; warp.hip kFastPitch, Fast<Cfg, 1>::kRows
+MAX_PITCH, LDS_ELEMS, MAX_ROWS = 256, 10240, 72  # warp_tile.h kMaxPitch, kLdsElems, 8 * kRowPasses (BlockCfg)
 GUARD, OFFSET = 4096, 8  # guard elements on each side; the stack starts 16 bytes past a 32-byte boundary
 
 SHAPES = [(56, 128), (120, 136), (113, 264), (128, 136)]
 
 
 def tile_h(H):
-    return 64 if H % 64 == 0 and H % 56 != 0 else 56  # warp.hip use_tile64
+    return 64 if H % 64 == 0 and H % 56 != 0 else 56  # warp_tile.h use_tile64
 
 
 def cv_round(v):
@@ -36,8 +36,8 @@ def cv_round(v):
 
 
 def source_box(Mi, xb, yb, H, W):
-    """warp.hip source_box + the plan kernel's fast-path test, for the inverted map Mi:
-    (mode, ax0, sy0, pitch, rows); mode 3 = fast staged path, 0 = general staged path,
+    """warp.hip source_box (affine_box of warp_tile.h, then box_plan) + the plan kernel's
+    fast-path test, for the inverted map Mi: (mode, ax0, sy0, pitch, rows); mode 3 = fast staged path, 0 = general staged path,
     1 = every tap outside, 2 = direct gather."""
     th = tile_h(H)
     xl, yl = min(xb + TILE_W, W) - 1, min(yb + th, H) - 1

@@ -61,7 +61,7 @@ def exact_sums(img, M):
 
 def tile_blend(img, M, xb=0, yb=0, tile_h=56):
     """The blend the one-channel fast path picks for the tile at (xb, yb) under a
-    translation-only map: the tile's staged box (source_box in warp.hip) and its bright
+    translation-only map: the tile's staged box (source_box in warp.hip, affine_box in warp_tile.h) and its bright
     16-byte chunks against kBrightShare = 20."""
     sx0, _, sy0, _ = fixed_point_origin(M)
     H, W = img.shape

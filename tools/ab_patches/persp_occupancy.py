@@ -7,7 +7,7 @@ import sys
 
 p = os.path.join(sys.argv[1], "warp.hip")
 s = open(p).read()
-a = "dim3(ntx, nty, n_frames), dim3(kThreads), 0, s, src, dst,\n                     plan, minv"
+a = "(warp_perspective_u16_kernel<C, Cfg>), tile_grid, dim3(kThreads), 0, s, src, dst"
 assert a in s
 pad = int(os.environ.get("KCMC_AB_PERSP_PAD", "3072"))
 s = s.replace(a, a.replace("dim3(kThreads), 0, s", f"dim3(kThreads), {pad}, s"))

@@ -1,16 +1,16 @@
 """Host audit of the warp's fixed-pitch staged path (mode 3, warp.hip): for every tile that
-warp_plan_kernel admits to mode 3, every tap that fast_rows / fastc_rows reads must lie in
+warp_plan_kernel admits to mode 3, every tap that fast_rows reads must lie in
 the rows and columns the staging wrote, and the packed (column, row) form must not wrap.
 
 The arithmetic is warp.hip's, restated in numpy float64 / int64 (the device code is built
 with -ffp-contract=off, and rint is round-half-even on both sides):
   * invert_affine (OpenCV's in-place inversion);
   * source_box + the mode-3 admission of warp_plan_kernel (C = 1: pitch <= 144 and
-    rows <= Fast<Cfg>::kRows; C = 3 / 4: pitch <= 144 and rows <= FastC<Cfg, C>::kRows);
-  * the row origins of the rowtab (X0(y), Y0(y)) and lane_cols' adelta / bdelta with the
+    rows <= Fast<Cfg, 1>::kRows; C = 3 / 4: pitch <= 144 and rows <= Fast<Cfg, C>::kRows);
+  * the row origins of the rowtab (X0(y), Y0(y)) and lane_columns' adelta / bdelta with the
     column clamp x = min(xb + 2 lane + q, W - 1);
-  * the staged area: rows [0, rows), columns [0, pitch) (fast_stage_land / fastc_stage_land
-    write every (row < rows, 8-px group < pitch / 8)).
+  * the staged area: rows [0, rows), columns [0, pitch) (Fast<Cfg, C>::land
+    writes every (row < rows, 8-px group < pitch / 8)).
 A tap (col, row) and its neighbours (col + 1, row + 1) must satisfy 0 <= col, col + 1 < pitch,
 0 <= row, row + 1 < rows, and the box-relative fixed-point X (and Y) must lie in [0, 2^26)
 so that the << 6 packing puts the integer part in the high half.
