@@ -325,7 +325,20 @@ int kcmc_ransac_model(kcmc_ctx* ctx, int model, const double* src_dev, const dou
  * reference's grayscale stacks), M_dev [n_frames, 2, 3] f64 forward maps (inverted
  * in double exactly as OpenCV does unless inverse_map != 0).  Out-of-image taps
  * read 0.  Bit-exact to the classic OpenCV fixed-point algorithm on platforms
- * without FMA contraction. */
+ * without FMA contraction.  A frame whose map holds a NaN is zeros.
+ * Alignment: src_dev and dst_dev need only the natural 2-byte alignment of uint16_t -- any
+ * element of a larger allocation may be the first (a tensor view, a frame range of a stack
+ * with odd W).  The kernels choose their 16-byte staging loads (W % 8 == 0), their buffer
+ * loads and stores through descriptors based at src_dev / dst_dev (the fast path) and their
+ * 4-byte pixel-pair stores (W even, or C = 3 / 4) from W alone, never from the pointers, so
+ * off the 16- / 4-byte grid these accesses are unaligned; that they return and write the right
+ * bytes rests on gfx950's unaligned global and buffer memory access (the driver's default
+ * unaligned access mode), not on code here.  Measured, not assumed: the seeded sweeps
+ * tests/test_gpu_sweeps.py::test_warp_affine_sweep / test_warp_perspective_sweep run both
+ * entries with sources 0, 2, 8 and 16 bytes and outputs 0 and 2 bytes off the grids on every
+ * staging and store path (tests/test_sweep_cases_host.py lists them), bit for bit against
+ * the oracle, the sources and outputs between sentinels.  The pipeline's own slabs start on
+ * frame boundaries of aligned allocations and never take the unaligned case. */
 int kcmc_warp_affine_u16(kcmc_ctx* ctx, const uint16_t* src_dev, uint16_t* dst_dev,
                          const double* M_dev, int n_frames, int H, int W, int C, int inverse_map,
                          kcmc_stream_t stream);
@@ -335,7 +348,10 @@ int kcmc_warp_affine_u16(kcmc_ctx* ctx, const uint16_t* src_dev, uint16_t* dst_d
  * reference's own warp is warpAffine, VA:458).  M_dev [n_frames, 3, 3] f64 forward maps,
  * inverted like cv::invert (closed-form 3x3) unless inverse_map != 0; classic
  * WarpPerspectiveInvoker fixed-point coordinates (per-block double evaluation, 1/32 px)
- * and the remapBilinear blend of kcmc_warp_affine_u16; out-of-image taps read 0. */
+ * and the remapBilinear blend of kcmc_warp_affine_u16; out-of-image taps read 0; a frame
+ * whose map holds a NaN is zeros.  Alignment as kcmc_warp_affine_u16: src_dev and dst_dev
+ * need only 2-byte alignment (the 16-byte staging loads with W % 8 == 0 and the 4-byte
+ * pixel-pair stores are then unaligned device accesses; pinned by the same sweep). */
 int kcmc_warp_perspective_u16(kcmc_ctx* ctx, const uint16_t* src_dev, uint16_t* dst_dev,
                               const double* M_dev, int n_frames, int H, int W, int C, int inverse_map,
                               kcmc_stream_t stream);

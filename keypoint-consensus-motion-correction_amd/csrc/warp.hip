@@ -215,9 +215,9 @@ __device__ __forceinline__ uint4 plane_piece(const uint32_t (&d)[4 * C]) {
 
 // Fast-path staging for C = 3 / 4 (round 4): issue() loads, land() stores and returns the wave's
 // count of bright (>= 16384) groups.  The interleaved box is de-interleaved while it lands:
-// each thread loads one 8-pixel group of a box row (C 16-byte chunks, 16-byte aligned because
-// ax0 and W are multiples of 8) and writes C planar 16-byte pieces (v_perm_b32 pairs), one per
-// channel plane, at the fixed pitch.  A pixel's taps then sit at the same offset in every plane
+// each thread loads one 8-pixel group of a box row (C 16-byte chunks, 16-byte aligned relative
+// to the frame because ax0 and W are multiples of 8, absolutely only when src is: kcmc.h) and
+// writes C planar 16-byte pieces (v_perm_b32 pairs), one per channel plane, at the fixed pitch.  A pixel's taps then sit at the same offset in every plane
 // (immediate offsets), so the coordinate work of a pixel is shared by its C channels, and each
 // lane's C output dwords (pixels 2l, 2l+1) leave in ONE 12- / 16-byte store: a wave's store
 // covers 768 / 1024 contiguous bytes of the row.  The general multi-channel path (mode 0) reads
@@ -620,7 +620,10 @@ __device__ __forceinline__ void output_rows(const uint16_t* stile, const TilePla
       // streaming store: the aligned frame is written once and not re-read by this kernel
       __builtin_nontemporal_store((uint32_t)o[0] | ((uint32_t)o[1] << 16), reinterpret_cast<uint32_t*>(drow));
     } else if (C >= 3 && x + 2 <= W) {
-      // two whole pixels: 6 (RGB) or 8 (RGBA) channels as 4-byte stores (x even -> aligned)
+      // two whole pixels: 6 (RGB) or 8 (RGBA) channels as 4-byte stores.  x is even, but drow
+      // is 4-byte aligned only where (y W + x) C is even and Dst itself is: on the odd rows
+      // of an RGB frame with odd W, or behind a Dst 2 bytes off the grid (as the pair store
+      // above), these are unaligned global stores, which gfx950 performs (kcmc.h, K3)
 #pragma unroll
       for (int k = 0; k < C; ++k)
         __builtin_nontemporal_store((uint32_t)o[2 * k] | ((uint32_t)o[2 * k + 1] << 16),
@@ -1018,7 +1021,8 @@ __device__ __forceinline__ void persp_rows(const uint16_t* stile, const TilePlan
       // streaming store: the aligned frame is written once and not re-read by this kernel
       __builtin_nontemporal_store((uint32_t)o[0] | ((uint32_t)o[1] << 16), reinterpret_cast<uint32_t*>(drow));
     } else if (C >= 3 && x + 2 <= W) {
-      // two whole pixels: 6 (RGB) or 8 (RGBA) channels as 4-byte stores (x even -> aligned)
+      // two whole pixels: 6 (RGB) or 8 (RGBA) channels as 4-byte stores; unaligned on the odd
+      // rows of an RGB frame with odd W and behind a Dst 2 bytes off the grid (see output_rows)
 #pragma unroll
       for (int k = 0; k < C; ++k)
         __builtin_nontemporal_store((uint32_t)o[2 * k] | ((uint32_t)o[2 * k + 1] << 16),
@@ -1174,7 +1178,10 @@ int with_linear_cfg(bool perspective, int C, int H, F f) {
   return perspective ? with_linear_cfg<true>(C, H, f) : with_linear_cfg<false>(C, H, f);
 }
 
-// The body of both entries.
+// The body of both entries.  Unlike run_tile_warp (warp_tile.h) it computes no vec_ok / pair_ok
+// from the pointers: the tile kernels vectorise by W alone and src / dst need only 2-byte
+// alignment, the unaligned 16- and 4-byte accesses being the device's business (kcmc.h;
+// pinned on and off the grids by the warp_affine / warp_perspective sweeps of tests/sweep_cases.py).
 int run_linear_warp(const char* name, const char* kernel_name, bool perspective, kcmc_ctx* ctx, const uint16_t* src,
                     uint16_t* dst, const double* M, int n_frames, int H, int W, int C, int inverse_map,
                     kcmc_stream_t stream) {

@@ -643,6 +643,12 @@ def warp_affine_u16(frames: torch.Tensor, affines: torch.Tensor, out: Optional[t
     frames [F, H, W] or [F, H, W, C] uint16 on the device; affines [F, 2, 3] f64.
     interpolation="cubic": the bicubic warp (K3c, build-defined: include/kcmc.h; parity with
     cv2 unpinned), grayscale [F, H, W] only.
+
+    frames and out are contiguous and may be views that start at any element of a larger
+    tensor: they need only uint16's 2-byte alignment.  The bilinear kernels then make their
+    16-byte loads and 4-byte stores unaligned, which rests on the device's unaligned global and
+    buffer access (include/kcmc.h) and is pinned by tests/test_gpu_sweeps.py::test_warp_affine_sweep.
+    A frame whose map holds a NaN is zeros.
     """
     check_interpolation(interpolation)
     if interpolation == "cubic" and frames.dim() == 4:
@@ -662,7 +668,11 @@ def warp_perspective_u16(frames: torch.Tensor, homographies: torch.Tensor, out: 
                          inverse_map: bool = False, stream: Optional[int] = None) -> torch.Tensor:
     """cv2.warpPerspective(frame, H, (W, H), INTER_LINEAR) for every frame (the warp of
     the homography extension).  frames [F, H, W] or [F, H, W, C] uint16; homographies
-    [F, 3, 3] f64 (forward maps, frame -> template, as RANSAC returns them)."""
+    [F, 3, 3] f64 (forward maps, frame -> template, as RANSAC returns them).
+
+    frames and out need only uint16's 2-byte alignment, as for warp_affine_u16 (views that start
+    at any element; unaligned device accesses, include/kcmc.h; pinned by
+    tests/test_gpu_sweeps.py::test_warp_perspective_sweep).  A frame whose map holds a NaN is zeros."""
     dev, out = _warp_args(frames, (3, 4), "frames must be [F, H, W] or [F, H, W, C]",
                           [(homographies, "homographies", torch.float64, (3, 3))], out)
     F, H, W = frames.shape[:3]

@@ -9,6 +9,8 @@ runs one case on the device and compares it with the numpy restatement, bit for 
     phase_sums          kcmc_bidi_phase_sums_u16                    (kcmc_amd.bidi)
     warp_field          kcmc_warp_field_u16                         (kcmc_amd.stages)
     resize_u8           kcmc_resize_u8                              (kcmc_amd.stages)
+    warp_affine         kcmc_warp_affine_u16, C = 1 / 3 / 4         (kcmc_amd.stages; against the C oracle)
+    warp_perspective    kcmc_warp_perspective_u16, C = 1 / 3 / 4    (kcmc_amd.stages; against the C oracle)
 
 case_<kernel>(seed) draws one case from np.random.default_rng(seed): the inputs as numpy arrays
 and the drawn parameters (describe(case): what a failure message prints).  expected(kernel, case)
@@ -23,11 +25,17 @@ Slabs: the stack is cut into 1 to 3 slabs, each a contiguous view that starts ``
 into its own allocation (u16: 0, 1, 4 or 8 -- 0, 2, 8 or 16 bytes; u8: 0 to 3), the reference
 image with an offset of its own.  Index lists: 0 to 8 entries with repeats, descending runs, -1
 and values >= F; every fourth seed the plain range(F), every sixteenth the empty list.
+
+The bilinear warps take any u16 pointer (include/kcmc.h): their sources sit between GUARD_U16
+fills (in front of an offset view and at least _GUARD elements behind the data), so that a
+staging load the device moved back onto the 16-byte grid, or one that strayed past the slab,
+reads values that are neither the frame's nor the border's zero, inside the allocation.
 """
 import ctypes
 
 import numpy as np
 
+import oracle
 import test_bidi_host as bhost
 import test_fallback_host as fhost
 import test_gpu_fuzz as fuzz
@@ -37,16 +45,20 @@ import test_quality_host as qhost
 import test_refine_field_host as tfhost
 import test_refine_host as rhost
 
+# _rng seeds from a kernel's position here: new kernels go at the end
 KERNELS = ("frame_stats", "shift_search", "gradient_sums", "tile_gradient_sums", "phase_sums", "warp_field",
-           "resize_u8")
+           "resize_u8", "warp_affine", "warp_perspective")
 # the seeds of tests/test_gpu_sweeps.py; tests/test_sweep_cases_host.py holds what they must reach
 SEEDS = {k: tuple(range(16)) for k in KERNELS}
+# seeds 0 to 15 hold no multichannel frame staged by mode 0 from a source 8 bytes off the 16-byte grid
+SEEDS["warp_affine"] = tuple(range(4, 20))
 # (kernel, seed) beyond SEEDS: cases a campaign (tools/kernel_sweeps.py) found failing, kept
 PINNED = ()
 
 OFFS_U16 = (0, 1, 4, 8)
 OFFS_U8 = (0, 1, 2, 3)
 FIELD_FAMILIES = ("zero", "2px", "40px", "constant", "2px+far")
+LINEAR_FAMILIES = ("fuzz", "near", "zoom-out")
 GUARD_U16, GUARD_U8 = 0xABCD, 0xA5
 _GUARD = 64  # sentinel elements in front of and behind an output
 
@@ -307,9 +319,86 @@ def case_resize_u8(seed):
     return case
 
 
+def _linear_map(rng, fam, H, W, C, persp, inverse_map):
+    """One frame's map of the bilinear sweeps.
+    fuzz: test_gpu_fuzz's families (for the perspective warp with its last rows, the one whose
+    denominator changes sign inside the frame among them: the direct gather).
+    near: a rotation of about 0.004 rad and a shift within 6 px (perspective: a last row of about
+    1e-5) -- a 128-px tile's box fits the 144-px fast pitch: mode 3 of the affine kernel, the
+    staged box and (H >= 16, W >= 64) the row table of the perspective one.
+    zoom-out: columns scaled by about 0.8 from the frame to the output (by its reciprocal in a map
+    that is passed as the inverse), so that a full tile's box is about 160 px wide, beyond
+    the fast pitch: the affine kernel's generic staging (mode 0); narrower edge tiles of the same
+    frame stay on mode 3.  The rows are zoomed in by about 1.3, or a full tile's box would not fit
+    its budget and the tile would gather (mode 2): a 64-row tile's 66 box rows x 168 exceed the 10240
+    elements of one channel, a 24-row tile's 26 x 168 x 4 the 16384 of four; 52 and 21 rows fit."""
+    if fam == "fuzz":
+        return (fuzz._perspective if persp else fuzz._affine)(rng, H, W)
+    a, t = rng.normal(0, 0.004), rng.uniform(-6, 6, 2)
+    sx, sy = 1.0, 1.0
+    if fam == "zoom-out":
+        sx, sy = rng.uniform(0.78, 0.84), rng.uniform(1.25, 1.4)
+        if inverse_map:
+            sx, sy = 1.0 / sx, 1.0 / sy
+    c, n = np.cos(a), np.sin(a)
+    M = np.array([[sx * c, -sy * n, t[0]], [sx * n, sy * c, t[1]]])
+    if persp:
+        M = np.vstack([M, [0.0, 0.0, 1.0]])
+        M[2, :2] = rng.normal(0, 1e-5, 2)
+    return M
+
+
+def _case_linear(kernel, seed):
+    """F in 1..3, H in 1..130, W in 1..300: up to three tile columns (128 px) and six tile rows (56
+    rows with one channel, 24 with three or four), interior, edge and partial tiles.  C follows
+    (1, 1, 3, 4)[seed % 4].  Every other seed is forced to W % 8 == 0 (the vector staging, mode 3),
+    the phase alternating every four seeds so that C = 1, 3 and 4 all get such seeds (of 0 to 15:
+    1, 4, 9, 12; 6, 14; 3, 11).  Those have W in 136..296, the first frame of every slab of the
+    zoom-out family (full tiles on mode 0 and, where the edge column is narrow, an edge tile on
+    mode 3: both stagings at the slab's offset) and the others of the near one; on the other
+    seeds W is _width's and every frame's family is drawn.  Affine with one channel: seed % 16 in
+    (1, 12) takes H in {64, 128} (the 64-row tiles).  seed % 5 == 4: a NaN entry in the last
+    frame's map.  inverse_map is drawn."""
+    persp = kernel == "warp_perspective"
+    rng = _rng(kernel, seed)
+    C = (1, 1, 3, 4)[seed % 4]
+    w8 = (seed + seed // 4) % 2 == 1
+    F, H, W = int(rng.integers(1, 4)), int(rng.integers(1, 131)), _width(rng, 1, 300)
+    if w8:
+        W = 8 * int(rng.integers(17, 38))
+    if not persp and C == 1 and seed % 16 in (1, 12):
+        H = int(rng.choice([64, 128]))
+    frames = _values(rng, (F, H, W * C)).reshape((F, H, W) if C == 1 else (F, H, W, C))
+    case = {"F": F, "H": H, "W": W, "C": C, "frames": frames, "slabs": _layout(rng, F, OFFS_U16)}
+    case["out_offs"] = [int(rng.choice(OFFS_U16)) for _ in case["slabs"]]
+    heads = {a for a, _, _ in case["slabs"]}
+    fams = [("zoom-out" if f in heads else "near") if w8 else LINEAR_FAMILIES[int(rng.integers(0, 3))]
+            for f in range(F)]
+    case["inverse_map"] = bool(rng.integers(0, 2))
+    M = np.stack([_linear_map(rng, fam, H, W, C, persp, case["inverse_map"]) for fam in fams])
+    if seed % 5 == 4:
+        M[F - 1, int(rng.integers(0, M.shape[1])), int(rng.integers(0, 3))] = np.nan
+    case["families"], case["M"] = fams, M
+    return case
+
+
+def case_warp_affine(seed):
+    return _case_linear("warp_affine", seed)
+
+
+def case_warp_perspective(seed):
+    return _case_linear("warp_perspective", seed)
+
+
+def frame_slab(case, f):
+    """(source offset, output offset) of the slab that holds frame f."""
+    return next((off, o) for (a, b, off), o in zip(case["slabs"], case.get("out_offs", [0] * 3)) if a <= f < b)
+
+
 GENERATORS = {"frame_stats": case_frame_stats, "shift_search": case_shift_search, "gradient_sums": case_gradient_sums,
               "tile_gradient_sums": case_tile_gradient_sums, "phase_sums": case_phase_sums,
-              "warp_field": case_warp_field, "resize_u8": case_resize_u8}
+              "warp_field": case_warp_field, "resize_u8": case_resize_u8, "warp_affine": case_warp_affine,
+              "warp_perspective": case_warp_perspective}
 
 
 def describe(case):
@@ -352,17 +441,24 @@ def expected(kernel, case):
         return {"out": phost.ref_warp_field(fr, case["M"], case["q"], (case["gy"], case["gx"]), case["inverse_map"])}
     if kernel == "resize_u8":
         return {"out": ohost.resize_np(fr, case["dst_h"], case["dst_w"])}
+    if kernel in ("warp_affine", "warp_perspective"):
+        # a frame whose map holds a NaN is zeros (include/kcmc.h; test_gpu_kernels.test_warp_nan_map_gives_zeros):
+        # the oracle, like OpenCV, converts the NaN coordinates to integers, which C leaves undefined
+        ref = oracle.warp_affine_u16 if kernel == "warp_affine" else oracle.warp_perspective_u16
+        return {"out": np.stack([np.zeros_like(fr[f]) if np.isnan(case["M"][f]).any() else
+                                 ref(fr[f], case["M"][f], inverse_map=case["inverse_map"]) for f in range(F)])}
     raise KeyError(kernel)
 
 
 # ------------------------------------------------------------------ the device's answers
-def _view(arr, off, dev, fill=0):
-    """``arr`` on the device as a contiguous view that starts ``off`` elements into its allocation."""
+def _view(arr, off, dev, fill=0, tail=0):
+    """``arr`` on the device as a contiguous view that starts ``off`` elements into its allocation;
+    the ``off`` elements in front of it and ``tail`` elements behind it hold ``fill``."""
     import torch
 
-    flat = np.full(off + arr.size, fill, arr.dtype)
-    flat[off:] = arr.reshape(-1)
-    return torch.from_numpy(flat).to(dev)[off:].view(*arr.shape)
+    flat = np.full(off + arr.size + tail, fill, arr.dtype)
+    flat[off:off + arr.size] = arr.reshape(-1)
+    return torch.from_numpy(flat).to(dev)[off:off + arr.size].view(*arr.shape)
 
 
 def _parts(case, dev):
@@ -382,13 +478,16 @@ def _guarded(shape, off, dtype, fill, dev):
     return buf, buf[_GUARD + off:_GUARD + off + n].view(*shape)
 
 
-def _per_slab(case, dev, dtype, fill, out_shape, call):
+def _per_slab(case, dev, dtype, fill, out_shape, call, src_guard=None):
     """call(slab tensor, first frame, end frame, out view) per slab into guarded outputs ->
-    (the outputs joined [F, ...], whether every sentinel survived)."""
+    (the outputs joined [F, ...], whether every sentinel survived).  src_guard: (fill, tail) of
+    the sources (_view); zeros in front and nothing behind without it."""
     outs, intact = [], True
     for (a, b, off), o_off in zip(case["slabs"], case["out_offs"]):
-        src = _view(case["frames"][a:b], off, dev)
+        src = _view(case["frames"][a:b], off, dev, *(src_guard or ()))
         buf, view = _guarded((b - a,) + out_shape, o_off, dtype, fill, dev)
+        for t, o in ((src, off), (view, o_off)):  # the 16-byte phases the case asks for
+            assert t.is_contiguous() and t.data_ptr() % 16 == (o * t.element_size()) % 16
         got = call(src, a, b, view)
         assert got.data_ptr() == view.data_ptr()
         flat, lo, n = buf.cpu().numpy(), _GUARD + o_off, view.numel()
@@ -404,6 +503,13 @@ def run(kernel, case, dev):
 
     from kcmc_amd import _intensity, _lib, bidi, fallback, quality, refine, stages
 
+    if kernel in ("warp_affine", "warp_perspective"):
+        fn = stages.warp_affine_u16 if kernel == "warp_affine" else stages.warp_perspective_u16
+        M = torch.from_numpy(case["M"]).to(dev)
+        call = lambda src, a, b, o: fn(src, M[a:b].contiguous(), out=o, inverse_map=case["inverse_map"])  # noqa: E731
+        out, ok = _per_slab(case, dev, torch.uint16, GUARD_U16, case["frames"].shape[1:], call,
+                            src_guard=(GUARD_U16, _GUARD))
+        return {"out": out, "guards": ok}
     if kernel in ("warp_field", "resize_u8"):
         if kernel == "warp_field":
             M, q = torch.from_numpy(case["M"]).to(dev), torch.from_numpy(case["q"]).to(dev)

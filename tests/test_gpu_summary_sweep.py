@@ -16,7 +16,10 @@ SEEDS = tuple(range(32))
 
 
 def case(seed):
-    rng = np.random.default_rng([len(sc.KERNELS), int(seed)])
+    # stream 7: the one behind sweep_cases' first seven kernels (once len(sc.KERNELS)); a literal,
+    # so that kernels appended there leave these cases as they are (warp_affine now seeds from
+    # the same stream, which harms neither)
+    rng = np.random.default_rng([7, int(seed)])
     F, H, W = int(rng.integers(1, 81)), int(rng.integers(1, 49)), sc._width(rng, 1, 48)
     c = sc._stack_case(rng, F, H, W, with_ref=False)
     c["rect"] = sc._rect(rng, H, W, 0, int(rng.integers(0, 8)))

@@ -1,6 +1,8 @@
 """Seeded random sweeps of the kernels added after the original hot path (the intensity passes,
 the field warp, the bidirectional-scan phase sums, the exact resize) against their numpy
-restatements, bit for bit: tests/sweep_cases.py draws the cases (shapes, rectangles, tilings,
+restatements, and of the two bilinear warps (one, three and four channels, sources and outputs
+on and off the 16- and 4-byte grids their vector loads and stores assume) against the C oracle,
+bit for bit: tests/sweep_cases.py draws the cases (shapes, rectangles, tilings,
 radii, fields, maps, slab layouts with misaligned starts, index lists with holes) and compares;
 tests/test_sweep_cases_host.py holds what the committed seeds reach.  Outputs with an ``out``
 argument are written into the middle of a sentinel-filled buffer whose sentinels must survive.
@@ -50,3 +52,13 @@ def test_warp_field_sweep(dev, seed):
 @pytest.mark.parametrize("seed", _seeds("resize_u8"))
 def test_resize_u8_sweep(dev, seed):
     sc.check("resize_u8", seed, dev)
+
+
+@pytest.mark.parametrize("seed", _seeds("warp_affine"))
+def test_warp_affine_sweep(dev, seed):
+    sc.check("warp_affine", seed, dev)
+
+
+@pytest.mark.parametrize("seed", _seeds("warp_perspective"))
+def test_warp_perspective_sweep(dev, seed):
+    sc.check("warp_perspective", seed, dev)

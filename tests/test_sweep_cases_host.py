@@ -12,6 +12,7 @@ import test_piecewise_host as phost
 import test_quality_host as qhost
 import test_refine_field_host as tfhost
 import test_refine_host as rhost
+import test_warp_linear_host as wl
 
 
 @pytest.fixture(scope="module")
@@ -131,6 +132,106 @@ def test_resize_seeds(cases):
     assert any(1 in (c["H"], c["W"], c["dst_h"], c["dst_w"]) for c in cs)
     assert any(c["dst_h"] == c["H"] or c["dst_w"] == c["W"] for c in cs)
     assert all(1 <= v <= 400 for c in cs for v in (c["H"], c["W"], c["dst_h"], c["dst_w"]))
+
+
+# ------------------------------------------------------------------ the bilinear warps
+# What the two sweeps are for: csrc/warp.hip decides its 16-byte staging loads, its buffer loads
+# and stores and its 4-byte pixel-pair stores from W alone, never from the pointers, so the seeds
+# must put every such access on and off its grid.  test_warp_linear_host restates both plan
+# kernels and names the tile kernels' paths; here every frame's paths are crossed with the
+# offsets of the slab that holds it.
+LINEAR = {"warp_affine": (wl.affine_paths, wl.AFFINE_PATHS), "warp_perspective": (wl.persp_paths, wl.PERSP_PATHS)}
+SRC_PHASES = {0: "on the grid", 8: "on the grid", 1: "2 bytes off", 4: "8 bytes off"}  # of 16 bytes, per OFFS_U16
+
+
+def linear_reach(kernel, cs):
+    """(paths, src, dst) of the frames of ``cs``.  paths: the union of the tile kernel's paths.
+    src: (group, mode, phase of the source slab on the 16-byte grid) of every vector-staged frame
+    -- W % 8 == 0 and a tile on mode 3 or mode 0; group vec1 / vecC by the channels.  dst: (kind,
+    output offset odd) of every dword-stored frame -- kind "pairs": C = 1, W even and a tile on
+    mode 0, 1 or 2 (a pixel pair as one dword); "channels": C = 3 or 4 and W >= 2 (two pixels as C
+    dwords; a frame whose map holds a NaN is stored by mode 1 like any other); "fast": a mode-3
+    tile (one b32 / b96 / b128 buffer store per lane)."""
+    paths_of = LINEAR[kernel][0]
+    paths, src, dst = set(), set(), set()
+    for c in cs:
+        for f in range(c["F"]):
+            p = paths_of(c["frames"][f], c["M"][f], c["inverse_map"])
+            off, o_off = sc.frame_slab(c, f)
+            paths |= set(p)
+            nan = "nan" in p  # every tile of the frame is on mode 1, whatever the restatement counted
+            for mode in ("mode3", "mode0"):
+                if c["W"] % 8 == 0 and mode in p and not nan:
+                    src.add(("vec1" if c["C"] == 1 else "vecC", mode, SRC_PHASES[off]))
+            if c["C"] == 1 and c["W"] % 2 == 0 and (nan or {"mode0", "mode1", "mode2"} & set(p)):
+                dst.add(("pairs", o_off % 2))
+            if c["C"] > 1 and c["W"] >= 2:
+                dst.add(("channels", o_off % 2))
+            if "mode3" in p and not nan:
+                dst |= {("fast", o_off % 2), (f"fast-C{c['C']}", o_off % 2)}  # the latter: b32, b96, b128
+    return paths, src, dst
+
+
+def linear_demands(kernel):
+    """What linear_reach of the committed seeds must hold: every path; each group of vector-staged
+    frames at each phase of the source, for the affine kernel on mode 3 and on mode 0 separately;
+    each kind of dword-stored frame at an even and at an odd output offset.  The perspective
+    kernel has no mode 3, hence neither that staging nor the "fast" stores."""
+    modes = ("mode3", "mode0") if kernel == "warp_affine" else ("mode0",)
+    kinds = ("pairs", "channels")
+    if kernel == "warp_affine":
+        kinds += ("fast", "fast-C1", "fast-C3", "fast-C4")  # and each width of the fast store by itself
+    src = {(g, m, ph) for g in ("vec1", "vecC") for m in modes for ph in set(SRC_PHASES.values())}
+    return LINEAR[kernel][1], src, {(k, odd) for k in kinds for odd in (0, 1)}
+
+
+@pytest.mark.parametrize("kernel", sorted(LINEAR))
+def test_linear_warp_seeds(cases, kernel):
+    cs = cases[kernel]
+    paths, src, dst = linear_reach(kernel, cs)
+    want_paths, want_src, want_dst = linear_demands(kernel)
+    assert paths == want_paths, (want_paths - paths, paths - want_paths)
+    assert src >= want_src, sorted(want_src - src)
+    assert dst >= want_dst, sorted(want_dst - dst)
+    # the draws of the generator's docstring
+    assert all(1 <= c["F"] <= 3 and 1 <= c["H"] <= 130 and 1 <= c["W"] <= 300 for c in cs)
+    assert all(c["C"] == (1, 1, 3, 4)[s % 4] for s, c in zip(sc.SEEDS[kernel], cs))
+    assert sum(c["W"] % 8 == 0 for c in cs) >= 8 and any(c["W"] % 2 for c in cs)
+    assert {c["C"] for c in cs if c["W"] % 8 == 0} == {1, 3, 4}  # the b32, b96 and b128 stores of mode 3
+    assert {fam for c in cs for fam in c["families"]} == set(sc.LINEAR_FAMILIES)
+    assert {c["inverse_map"] for c in cs} == {False, True}
+    assert any(np.isnan(c["M"][-1]).any() for c in cs) and not any(np.isnan(c["M"][:-1]).any() for c in cs)
+    assert any(-(-c["W"] // 128) == 3 for c in cs)  # three tile columns
+    # a tile is 128 x 56 (x 64) with one channel and 128 x 24 with more: a case is small
+    assert all(c["frames"].size <= 3 * 130 * 300 * 4 for c in cs)
+
+
+def test_linear_warp_sources_are_guarded_and_compare_is_sensitive():
+    """Without a device: the source views sit between nonzero fills inside their allocations, and
+    compare refuses an output that is off by one in one pixel, and one whose sentinels are gone."""
+    import torch
+
+    cpu = torch.device("cpu")
+    arr = np.arange(1, 25, dtype=np.uint16).reshape(2, 3, 4)
+    for off in sc.OFFS_U16:
+        v = sc._view(arr, off, cpu, sc.GUARD_U16, sc._GUARD)
+        flat = torch.as_strided(v, (off + arr.size + sc._GUARD,), (1,), v.storage_offset() - off).numpy()
+        assert v.is_contiguous() and v.storage_offset() == off and np.array_equal(v.numpy(), arr)
+        assert (flat[:off] == sc.GUARD_U16).all() and (flat[off + arr.size:] == sc.GUARD_U16).all()
+        assert len(flat[off + arr.size:]) >= 64
+    z = sc._view(arr, 4, cpu)  # the other kernels' views: zeros in front, nothing behind
+    assert z.storage_offset() == 4 and z.untyped_storage().nbytes() == 2 * (4 + arr.size)
+    for kernel in sorted(LINEAR):
+        c = next(c for c in map(sc.GENERATORS[kernel], sc.SEEDS[kernel]) if c["frames"].size > 1000)
+        want = sc.expected(kernel, c)
+        assert want["out"].shape == c["frames"].shape and want["out"].dtype == np.uint16
+        sc.compare(kernel, c, {"out": want["out"].copy(), "guards": True}, want)
+        wrong = want["out"].copy()
+        wrong.reshape(-1)[wrong.size // 2] ^= 1  # one pixel, by one
+        with pytest.raises(AssertionError):
+            sc.compare(kernel, c, {"out": wrong, "guards": True}, want)
+        with pytest.raises(AssertionError):
+            sc.compare(kernel, c, {"out": want["out"].copy(), "guards": False}, want)
 
 
 @pytest.mark.parametrize("kernel", sc.KERNELS)
