@@ -42,6 +42,8 @@
  *   kcmc_bidi_phase_sums_u16 / kcmc_shift_rows_u16 <- nothing in the reference (an extension):
  *                             the offset of the odd rows of a bidirectionally scanned stack
  *                             against its even rows, measured and undone before registration.
+ *   kcmc_box_bandpass_u16  <- nothing in the reference (an extension): the detection copy of a
+ *                             stack, box-smoothed with a box background removed.
  *
  * Conventions
  *   - Plain pointers and sizes only.  Pointers named *_dev are device (HBM) pointers
@@ -735,6 +737,43 @@ int kcmc_bidi_phase_sums_u16(kcmc_ctx* ctx, const uint16_t* frames_dev, int n_fr
  * completely before any of it is written.  Asynchronous on `stream`, no allocation. */
 int kcmc_shift_rows_u16(kcmc_ctx* ctx, const uint16_t* src_dev, uint16_t* dst_dev, int n_frames, int H, int W,
                         int parity, int d, kcmc_stream_t stream);
+
+/* ----------------------------- p1: box band-pass prefilter in front of keypoint detection
+ * Build-defined: the reference has no such mode.  The detection copy of a uint16 stack: a small
+ * box smoothing minus a large box background, floored at 0 (host part: kcmc_amd.prefilter; numpy
+ * restatement: tests/test_prefilter_host.py).  Two integer radii: s = smooth_radius in [0, 4], r =
+ * background_radius, 0 or in [s + 1, 32]; not both 0.  For one frame src[H][W], a radius rho and the
+ * pixel (y, x) the window is clipped to the image (rho = 0: the pixel itself):
+ *
+ *   rows y0 = max(0, y - rho) .. y1 = min(H - 1, y + rho), columns x0 = max(0, x - rho) .. x1 = min(W - 1, x + rho)
+ *   n_rho = (y1 - y0 + 1) (x1 - x0 + 1)
+ *   S_rho = the sum of src over the window              <= 65535 * 65^2 < 2^32
+ *   m_rho = (S_rho + n_rho / 2) / n_rho                 the rounded mean, integer division
+ *
+ *   a = m_s,  b = r > 0 ? m_r : 0,  dst[y][x] = max(a - b, 0)
+ *
+ * The box of ones in the denominator makes a constant frame filter to 0 right up to the border
+ * (r > 0; to itself with r = 0); the floor at 0 keeps the bright features for the percentile
+ * scaling that follows.  Once r >= max(H, W) - 1 every pixel's background is the rounded mean of
+ * the whole frame.  Frames are independent; src_dev / dst_dev [n_frames, H, W] u16.
+ *
+ * Contract (KCMC_EINVAL before any device work otherwise): ctx not NULL, n_frames >= 0, H >= 1,
+ * W >= 1 (frames smaller than the window are fine), the radii as above; with n_frames > 0 also
+ * src_dev and dst_dev not NULL and the two stacks must not overlap (a neighbourhood filter cannot
+ * run in place).  n_frames == 0 is KCMC_OK once the shape and the radii have passed: nothing is
+ * touched and the two pointers are not looked at (they may be NULL).  Any 2-byte aligned pointers
+ * and any W; frame offsets are 64-bit.  No load or store leaves the two stacks.  Exact integers
+ * throughout, so the result does not depend on how the work is cut.  Asynchronous on `stream`, no
+ * allocation. */
+int kcmc_box_bandpass_u16(kcmc_ctx* ctx, const uint16_t* src_dev, uint16_t* dst_dev, int n_frames, int H, int W,
+                          int smooth_radius, int background_radius, kcmc_stream_t stream);
+
+/* How kcmc_box_bandpass_u16 cuts that call's work, for tests and tools that want shapes at the
+ * kernel's seams: plan_host[4] = (output columns of one workgroup's strip, strips per frame, row
+ * chunks per frame, rows per chunk).  Every chunk holds at least one row: (chunks - 1) * rows < H <=
+ * chunks * rows.  The same checks of the shape and the radii; host only, no context, no device
+ * work. */
+int kcmc_box_bandpass_plan(int n_frames, int H, int W, int smooth_radius, int background_radius, int* plan_host);
 
 #ifdef __cplusplus
 }

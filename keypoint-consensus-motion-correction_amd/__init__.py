@@ -9,10 +9,10 @@ include/kcmc.h); the host keeps the reference's Python API.
 Import as ``import kcmc_amd`` (the repository-root shim ``kcmc_amd.py`` maps that
 name onto this directory).
 """
-from . import bidi, fallback, piecewise, quality, refine, refine_field, summary
+from . import bidi, fallback, piecewise, prefilter, quality, refine, refine_field, summary
 from .affines import AlignmentError
 from .video_aligner import LoResVideoAligner, VideoAligner
 
-__all__ = ["VideoAligner", "LoResVideoAligner", "AlignmentError", "bidi", "fallback", "piecewise", "quality", "refine",
-           "refine_field", "summary"]
+__all__ = ["VideoAligner", "LoResVideoAligner", "AlignmentError", "bidi", "fallback", "piecewise", "prefilter",
+           "quality", "refine", "refine_field", "summary"]
 __version__ = "0.1.0"

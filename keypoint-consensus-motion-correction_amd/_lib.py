@@ -67,6 +67,8 @@ EXPORTED_SYMBOLS = (
     "kcmc_bidi_phase_sums_u16",
     "kcmc_shift_rows_u16",
     "kcmc_temporal_sums_u16",
+    "kcmc_box_bandpass_u16",
+    "kcmc_box_bandpass_plan",
 )
 
 KCMC_MODEL_EUCLIDEAN = 0
@@ -144,6 +146,8 @@ _SIGNATURES = {
     "kcmc_bidi_phase_sums_u16": ([P, P, I, I, I, P, I, I, P, P], I),
     "kcmc_shift_rows_u16": ([P, P, P, I, I, I, I, I, P], I),
     "kcmc_temporal_sums_u16": ([P, P, I, I, I, P, I, I, I, I, I, P, P, P], I),
+    "kcmc_box_bandpass_u16": ([P, P, P, I, I, I, I, I, P], I),
+    "kcmc_box_bandpass_plan": ([I, I, I, I, I, P], I),
 }
 
 

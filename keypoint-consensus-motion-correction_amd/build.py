@@ -17,7 +17,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 REPO = os.path.dirname(PKG_DIR)
 LIB_PATH = os.path.join(PKG_DIR, "libkcmc.so")
 OFFLOAD_ARCH = os.environ.get("KCMC_OFFLOAD_ARCH", "gfx950")
-SOURCES = ["bidi_phase.hip", "capi.cpp", "consensus.hip", "hostalg.cpp", "match.hip", "match_f32.hip", "match_filter.hip", "match_hamming.hip", "normalize.hip", "orb.hip", "pyramid.hip", "quality.hip", "ransac.hip", "ransac_model.hip", "refine.hip", "refine_tiles.hip", "resize.hip", "shift_search.hip", "temporal_sums.hip", "warp.hip", "warp_cubic.hip", "warp_field.hip"]
+SOURCES = ["band_filter.hip", "bidi_phase.hip", "capi.cpp", "consensus.hip", "hostalg.cpp", "match.hip", "match_f32.hip", "match_filter.hip", "match_hamming.hip", "normalize.hip", "orb.hip", "pyramid.hip", "quality.hip", "ransac.hip", "ransac_model.hip", "refine.hip", "refine_tiles.hip", "resize.hip", "shift_search.hip", "temporal_sums.hip", "warp.hip", "warp_cubic.hip", "warp_field.hip"]
 HEADERS = ["kcmc_internal.h", "match_common.h", "ransac_common.h", "u16_rows.h", "warp_common.h", "warp_tile.h", os.path.join("..", "..", "include", "kcmc.h")]
 
 COMMON_FLAGS = [

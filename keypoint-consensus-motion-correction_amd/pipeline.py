@@ -916,16 +916,32 @@ def downsample_u8(frames_u8: torch.Tensor, template_u8: torch.Tensor, frame_down
 
 
 def detect_slab(frames: torch.Tensor, cfg: AlignConfig, template_index: Optional[int] = None,
-                template: Optional[torch.Tensor] = None, orb_params=None, percentile: float = 99.99):
+                template: Optional[torch.Tensor] = None, orb_params=None, percentile: float = 99.99,
+                prefilter: Optional[Tuple[int, int]] = None):
     """The front end of align_images (VA:93-123) on the device for a uint16 stack:
     normalisation (f2: exact 99.99th percentile + max-scale) and the build's
     ORB-style detector (f1) on the template and on every sample frame.  Returns
-    (SlabInputs for align_slab, brightest)."""
+    (SlabInputs for align_slab, brightest).  ``prefilter`` = (s, r): the percentile, the
+    max-scaling and the detection read the band-passed copy of the stack and of ``template``
+    (kcmc_amd.prefilter, p1), released once the uint8 stack exists; the SlabInputs carry the raw
+    frames.  None: off."""
     if frames.dim() != 3:
         raise ValueError("detection needs a grayscale stack [F, H, W]")
     F = frames.shape[0]
-    brightest = stages.brightest_px(frames, percentile)
-    u8 = stages.max_scale_u8(frames, brightest)
+    seen = frames
+    if prefilter is not None:
+        from . import prefilter as _pf
+
+        s, r = _pf.check_radii(*prefilter)
+        seen = _pf.box_bandpass(frames.contiguous(), s, r)
+        if template is not None:
+            template = _pf.box_bandpass(template.reshape(1, *template.shape[-2:]).contiguous(), s, r)
+    brightest = stages.brightest_px(seen, percentile)
+    if prefilter is not None and not brightest > 0:
+        raise _aff.AlignmentError(f"the band-pass prefilter (smoothing radius {s}, background radius {r}) leaves "
+                                  f"nothing of the stack: its {percentile}th percentile is 0")
+    u8 = stages.max_scale_u8(seen, brightest)
+    del seen
     if template is None:
         ti = int(F * 0.5) if template_index is None else int(template_index)
         tpl_u8 = u8[ti:ti + 1]
@@ -943,11 +959,13 @@ def detect_slab(frames: torch.Tensor, cfg: AlignConfig, template_index: Optional
 
 def align_frames(frames: torch.Tensor, cfg: AlignConfig, template_index: Optional[int] = None,
                  orb_params=None, out: Optional[torch.Tensor] = None,
-                 logger: Optional[logging.Logger] = None) -> SlabResult:
+                 logger: Optional[logging.Logger] = None,
+                 prefilter: Optional[Tuple[int, int]] = None) -> SlabResult:
     """align_images (VA:57-158) entirely on the device for a device-resident uint16 stack:
     normalisation, detection, matching, consensus (host, native), RANSAC, gap filling
-    (host) and warp."""
-    inp, brightest = detect_slab(frames, cfg, template_index, orb_params=orb_params)
+    (host) and warp.  ``prefilter`` = (s, r): detection on the band-passed copy (detect_slab),
+    the warp on the raw frames."""
+    inp, brightest = detect_slab(frames, cfg, template_index, orb_params=orb_params, prefilter=prefilter)
     res = align_slab(inp, cfg, logger=logger, out=out)
     res.extras["brightest"] = brightest
     res.extras["n_template_keypoints"] = int(inp.des_tpl.shape[0])

@@ -36,6 +36,7 @@ from . import fallback as _fb
 from . import multidevice as _md
 from . import piecewise as _pw
 from . import pipeline as _pl
+from . import prefilter as _pf
 from . import quality as _q
 from . import refine as _rf
 from . import refine_field as _rff
@@ -253,6 +254,28 @@ class VideoAligner:
     BIDI_PHASE_RADIUS = 8           # 1..16 px
     BIDI_PHASE_FRAMES = 64          # >= 1
     BIDI_PHASE_MIN_GAIN = 0.0
+    # New (opt-in, kcmc_amd.prefilter; build-defined, the reference has no such mode): a box
+    # band-pass in front of the keypoint detection, for one-photon / miniscope / widefield stacks
+    # (cells a few hundred grey levels high on a background of tens of thousands: after the
+    # max-scaling FAST sees the vignette only) and for shot-noise-limited frames.  Both 0: off,
+    # nothing runs and nothing is allocated.  DETECT_SMOOTH_RADIUS s in [0, 4],
+    # DETECT_BACKGROUND_RADIUS r either 0 or in [s + 1, 32]: align_images detects on a copy of the
+    # stack with every pixel replaced by max(m_s - m_r, 0) -- m_rho the rounded mean over the
+    # (2 rho + 1)^2 box clipped to the image, m_r = 0 with r = 0 (csrc/band_filter.hip,
+    # include/kcmc.h) -- made after BIDI_PHASE has corrected the stack.  The copy feeds the
+    # percentile, the max-scaling, the downsample and the detection (GPU or host detector); the
+    # template frame is taken from it, a masked_template and the refined template of
+    # TEMPLATE_REFINE_ITERS are filtered the same way (template_image stays the mean of the raw
+    # aligned frames).  Every warp and every later pass -- the fallback, the refinements, the
+    # metrics, the summary images -- reads the raw (phase-corrected) stack as without the switch:
+    # the transforms, affines, skipped_idxs and interpolated_idxs are what the plain aligner
+    # returns for the filtered stack, aligned_imgs is the raw stack warped by those maps.  The
+    # copy is released once the uint8 stack exists: the peak device memory per slab is raw +
+    # filtered + uint8.  A stack the filter flattens completely (its percentile is 0) is an
+    # AlignmentError.  align_keypoints has no detection to feed: it validates the constants and
+    # ignores them.  Results: prefilter_radii, prefilter_brightest_px.  Grayscale stacks.
+    DETECT_SMOOTH_RADIUS = 0
+    DETECT_BACKGROUND_RADIUS = 0
 
     def __init__(self, logger: LoggerAdapter = None):
         self.logger = logger
@@ -270,6 +293,7 @@ class VideoAligner:
         self._reset_fallback()
         self._reset_refine()
         self._reset_bidi()
+        self._reset_prefilter()
 
     # ------------------------------------------------------------------ helpers
     @classmethod
@@ -411,6 +435,57 @@ class VideoAligner:
                     template = _as_numpy(p[template_idx - f0])
                 f0 += p.shape[0]
         return parts, template
+
+    # ------------------------------------------------- band-pass prefilter of the detection
+    def _reset_prefilter(self) -> None:
+        self.prefilter_radii = None
+        self.prefilter_brightest_px = None
+
+    def _prefilter_on(self, images=None) -> Optional[Tuple[int, int]]:
+        """(s, r) of DETECT_SMOOTH_RADIUS / DETECT_BACKGROUND_RADIUS, None with both 0, after the
+        checks that must fail before any work (``images``: only its number of dimensions is read,
+        when it has one)."""
+        s, r = self.DETECT_SMOOTH_RADIUS, self.DETECT_BACKGROUND_RADIUS
+        if _pf._is_int(s) and _pf._is_int(r) and int(s) == 0 and int(r) == 0:
+            return None
+        try:
+            radii = _pf.check_radii(s, r)
+        except ValueError as e:
+            raise ValueError(f"DETECT_SMOOTH_RADIUS / DETECT_BACKGROUND_RADIUS: {e}") from None
+        if getattr(images, "ndim", 3) != 3:
+            raise NotImplementedError("DETECT_SMOOTH_RADIUS / DETECT_BACKGROUND_RADIUS support grayscale stacks "
+                                      "[F, H, W] only")
+        return radii
+
+    def _prefilter_image(self, image_u16) -> np.ndarray:
+        """One [H, W] uint16 image in the detection's intensity domain: filtered on the first device
+        of the hot path with the switch on, as given with it off."""
+        radii = self._prefilter_on()
+        image = _as_numpy(image_u16)
+        if radii is None:
+            return image
+        with torch.cuda.device(self._device()):
+            t = torch.from_numpy(np.ascontiguousarray(image, np.uint16)[None]).to(self._device())
+            return _pf.box_bandpass(t, *radii)[0].cpu().numpy()
+
+    def _prefilter_source(self, parts: List[torch.Tensor], template, template_idx: Optional[int]):
+        """(the slabs the detection reads, the template in their domain): ``parts`` and ``template``
+        themselves with the switch off; with it on, the filtered copies of the slabs and the
+        template frame taken from them (``template_idx``; None: a masked_template, filtered by the
+        same call)."""
+        radii = self._prefilter_on()
+        if radii is None:
+            return parts, template
+        self.prefilter_radii = radii
+        filtered = _pf.box_bandpass([p.contiguous() for p in parts], *radii)
+        if template_idx is None:
+            return filtered, self._prefilter_image(template)
+        f0 = 0
+        for p in filtered:
+            if f0 <= template_idx < f0 + p.shape[0]:
+                template = _as_numpy(p[template_idx - f0])
+            f0 += p.shape[0]
+        return filtered, template
 
     # ------------------------------------------------------------- piecewise-rigid correction
     def _reset_piecewise(self) -> None:
@@ -686,6 +761,8 @@ class VideoAligner:
         self._interpolation_on(images)
         self._reset_bidi()
         self._bidi_on(images)
+        self._reset_prefilter()
+        self._prefilter_on(images)
         self._reset_quality()
         self._quality_on(refine_supported)
         self._reset_summary()
@@ -714,7 +791,10 @@ class VideoAligner:
         rotation, scale).  A device tensor input yields a device tensor output.
 
         With BIDI_PHASE on, the template frame is taken from the corrected stack; a
-        ``masked_template`` is used as given (the caller corrects it, bidi.shift_rows).
+        ``masked_template`` is used as given (the caller corrects it, bidi.shift_rows).  With
+        DETECT_SMOOTH_RADIUS / DETECT_BACKGROUND_RADIUS set, the detection reads the band-passed
+        copy of the stack and of the template (a ``masked_template`` is passed raw and filtered
+        here); the returned frames are the raw stack warped.
         """
         self._begin(images, refine_supported=True)
         self.logger.info(f"aligning {len(images)} frames with n_kp_global: {n_kp_global} and {detector_algorithm}")
@@ -738,11 +818,21 @@ class VideoAligner:
         assert (images.dtype == torch.uint16) if on_device else (np.asarray(images).dtype == np.uint16)  # VA:104
         parts, ranges = self._split(images, rate)
         parts, template = self._bidi_source(parts, not on_device, template, template_idx)
-        brightest_px = stages.brightest_px(parts, self.IMAGE_NORM_MAX_PERCENTILE)
+        # the detection's source: the stack itself, or its band-passed copy (the warps read `parts`)
+        seen, template = self._prefilter_source(parts, template, template_idx)
+        brightest_px = stages.brightest_px(seen, self.IMAGE_NORM_MAX_PERCENTILE)
+        if self.prefilter_radii is not None:
+            self.prefilter_brightest_px = brightest_px
+            if not brightest_px > 0:
+                raise AlignmentError(
+                    f"the band-pass prefilter (DETECT_SMOOTH_RADIUS = {self.prefilter_radii[0]}, "
+                    f"DETECT_BACKGROUND_RADIUS = {self.prefilter_radii[1]}) leaves nothing of the stack: its "
+                    f"{self.IMAGE_NORM_MAX_PERCENTILE}th percentile is 0")
         u8_parts = []
-        for p in parts:  # each slab's work under its own device (launches, workspaces, allocations)
+        for p in seen:  # each slab's work under its own device (launches, workspaces, allocations)
             with _md._on(p):
                 u8_parts.append(self._max_scale_images(p, None, brightest_px, np.uint8)[0])
+        del seen, p  # a filtered copy is released here: raw + filtered + uint8 is the peak per slab
         _, template_i8 = self._max_scale_images(None, template, brightest_px, np.uint8)
         detector = self.DETECTOR_CONSTRUCTOR_DICT[detector_algorithm]()
         on_gpu = isinstance(detector, GpuOrbDetector) and parts[0].dim() == 3
@@ -789,6 +879,7 @@ class VideoAligner:
         self.logger.info(f"identified keypoints in: {round(time.time() - t_start)} s")
 
         def detect_template(tpl_u16):  # as a masked_template enters, on the first slab's device
+            tpl_u16 = self._prefilter_image(tpl_u16)
             t8 = np.ascontiguousarray(self._max_scale_images(None, tpl_u16, brightest_px, np.uint8)[1])
             with _md._on(u8_parts[0]):
                 t8 = torch.from_numpy(t8).to(u8_parts[0].device)[None]
@@ -810,8 +901,10 @@ class VideoAligner:
 
     def _host_template_detector(self, detector, brightest_px, rate) -> Callable:
         """template_u16 -> (kp, des) with a host (OpenCV-style) detector, the way a
-        masked_template enters align_images: max-scale, downsample, detectAndCompute."""
+        masked_template enters align_images: the prefilter when it is on, max-scale, downsample,
+        detectAndCompute."""
         def detect_template(tpl_u16):
+            tpl_u16 = self._prefilter_image(tpl_u16)
             t8 = self._max_scale_images(None, tpl_u16, brightest_px, np.uint8)[1]
             t8 = self._downsample(t8[None], t8, rate, self.SPATIAL_DOWNSAMPLE_RATE)[1]
             kp_t, des_t = detector.detectAndCompute(t8, None)
@@ -871,6 +964,9 @@ class VideoAligner:
         (images[::max(1, frame_rate // FRAME_SAMPLE_RATE)]) keypoint coordinates [n, 2]
         and uint8 descriptors [n, D]; template keypoints/descriptors likewise."""
         self._begin(images, refine_supported=False)
+        if self._prefilter_on() is not None:
+            self.logger.info("DETECT_SMOOTH_RADIUS / DETECT_BACKGROUND_RADIUS: ignored by align_keypoints (the "
+                             "keypoints are given, there is no detection to filter for)")
         self._kp_template = np.asarray(kp_template, dtype=np.float64).reshape(-1, 2)
         self._des_template = np.asarray(des_template, dtype=np.uint8)
         rate = max(1, frame_rate // self.FRAME_SAMPLE_RATE)
