@@ -139,20 +139,79 @@ __device__ __forceinline__ void ransac_rigid_frame(
     return;
   const uint32_t* H = hyp + hoff;
 
-  // LDS: sx, sy, dx, dy [N] f64 | the points as (x, y, u, v) [N] f32x4 | trial S (low bound)
-  //      [T] f64 | trial S high bound [T] f64 | [LARGE: stack [kMaxStack][256] f64]
-  //      | per-wave leaf values [4][128] f64 | trial count [T] i32 | inlier flags [N] u8
+  // LDS, LARGE: sx, sy, dx, dy [N] f64 | the points as (x, y, u, v) [N] f32x4 | trial S (low
+  //      bound) [T] f64 | trial S high bound [T] f64 | stack [kMaxStack][256] f64 | per-wave
+  //      leaf values [4][128] f64 | trial count [T] i32 | inlier flags [N] u8
+  // N <= 128 (ransac_common.h rigid_small_lds; at N = 128, T = 1000 the workgroup takes 18,336
+  // B of dynamic LDS, inside the 20 KiB a retiring warp tile frees): sx, sy, dx, dy [N] f64 |
+  //      a region that holds the f32x4 points in phase A and the per-wave leaf values [4][N]
+  //      f64 in phase B (phase A is the only reader of the fp32 points, phase B the only
+  //      writer of the leaf values, barriers between) | a trial's bracket as two floats
+  //      rounded outward [T] f32 x 2 | certain count, undecided count [T] u8 x 2 | inlier
+  //      flags [N] u8.  The exact path's records (S [T] f64, count [T] i32) lie over the
+  //      region and the compact records: it starts behind a barrier after the last read of both.
+  // Outward rounding keeps every bracket a bound on numpy's S: lo' <= lo <= S <= hi <= hi'.
+  // The trial with the smallest S at the best count, S*, has lo'* <= S* <= S_t <= hi'_t for
+  // every trial t at that count, so it -- and every trial that ties it -- stays a phase-B
+  // candidate (lo' <= min hi'); phase B scores each candidate exactly and selects on the exact
+  // values, so wider brackets add candidates and change no output.  The brackets' validity
+  // tests (1e-30 .. 1e30, which also send every S == 0 to the exact path) see the rounded values.
   double* sx = smem;
   double* sy = sx + N;
   double* dxs = sy + N;
   double* dys = dxs + N;
   float4* pk32 = reinterpret_cast<float4*>(dys + N);  // 16-byte aligned: 4 N doubles before it
-  double* tS = reinterpret_cast<double*>(pk32 + N);
-  double* tSh = tS + T;
+  double* tS = reinterpret_cast<double*>(pk32 + (LARGE ? N : 0));
+  double* tSh = tS + T;  // LARGE only
   double* stk = tSh + T;
-  double* wvals = stk + (LARGE ? kMaxStack * kThreads : 0);
-  int* tC = reinterpret_cast<int*>(wvals + kThreads / 64 * 128);
-  uint8_t* inl = reinterpret_cast<uint8_t*>(tC + T);
+  double* wvals = LARGE ? stk + kMaxStack * kThreads : tS;
+  int* tC = reinterpret_cast<int*>(LARGE ? wvals + kThreads / 64 * 128 : tS + T);
+  float* fLo = reinterpret_cast<float*>(tS + 4 * N);  // N <= 128 only, and the three below
+  float* fHi = fLo + T;
+  uint8_t* bC = reinterpret_cast<uint8_t*>(fHi + T);
+  uint8_t* bU = bC + T;
+  uint8_t* inl = LARGE ? reinterpret_cast<uint8_t*>(tC + T)
+                       : reinterpret_cast<uint8_t*>(tS) + max(32 * N + 10 * T, 12 * T);
+  // a trial's phase-A record: v = pack_cnt(certain, undecided), -1 (no model) or INT_MIN
+  // (deferred to the fp64 phase A), and the bracket of its S
+  auto rec_put = [&](int t, int v, double slo, double shi) {
+    if constexpr (LARGE) {
+      tC[t] = v;
+      tS[t] = slo;
+      tSh[t] = shi;
+    } else {
+      bC[t] = v == INT_MIN ? kDeferred : v < 0 ? kNoModel : (uint8_t)(v & 0xffff);
+      bU[t] = (uint8_t)und_of(v);
+      fLo[t] = (float)slo;  // exact: outward() rounded both
+      fHi[t] = (float)shi;
+    }
+  };
+  auto outward = [&](double& slo, double& shi) {
+    if constexpr (!LARGE) {
+      slo = (double)f32_below(slo);
+      shi = (double)f32_above(shi);
+    }
+  };
+  auto rec_cnt = [&](int t) {
+    if constexpr (LARGE) return cnt_of(tC[t]);
+    else return cnt_of8(bC[t]);
+  };
+  auto rec_und = [&](int t) {
+    if constexpr (LARGE) return und_of(tC[t]);
+    else return bC[t] >= kDeferred ? 0 : (int)bU[t];
+  };
+  auto rec_deferred = [&](int t) {
+    if constexpr (LARGE) return tC[t] == INT_MIN;
+    else return bC[t] == kDeferred;
+  };
+  auto rec_lo = [&](int t) {
+    if constexpr (LARGE) return tS[t];
+    else return (double)fLo[t];
+  };
+  auto rec_hi = [&](int t) {
+    if constexpr (LARGE) return tSh[t];
+    else return (double)fHi[t];
+  };
   if (LARGE && tid == 0) {
     s_plan.n = 0;
     plan_gen<kPwDepth>(s_plan, 0, N);
@@ -239,29 +298,27 @@ __device__ __forceinline__ void ransac_rigid_frame(
         int clo = 0, chi = 0;
         const float S32 = score32(pk32, N, L, clo, chi);
         s32_bracket(S32, N, L.be, slo, shi);
+        outward(slo, shi);
         v = pack_cnt(clo, chi - clo);
         if (!(slo >= 1e-30 && shi <= 1e30)) flag = 1;
       } else if (m.ok) {
         v = INT_MIN;
         deferred = true;
       }
-      tC[t] = v;
-      tS[t] = slo;
-      tSh[t] = shi;
+      rec_put(t, v, slo, shi);
       mlo = max(mlo, cnt_of(v));
     }
     if (deferred) {
       for (int t = tid; t < T; t += kThreads) {
-        if (tC[t] != INT_MIN) continue;
+        if (!rec_deferred(t)) continue;
         const Model m = fit_of(t);
         int cnt = 0;
         const float S32 = score_fast(m, P, N, tq, cnt);
         double slo, shi;
         s64_bracket(S32, N, slo, shi);
+        outward(slo, shi);
         if (!(slo >= 1e-30 && shi <= 1e30)) flag = 1;
-        tC[t] = cnt;
-        tS[t] = slo;
-        tSh[t] = shi;
+        rec_put(t, cnt, slo, shi);
         mlo = max(mlo, cnt);
       }
     }
@@ -270,7 +327,7 @@ __device__ __forceinline__ void ransac_rigid_frame(
     // phase A2: the exact count of every trial the undecided points could lift to mlo, each
     // by a whole wave (the points over the lanes, fp64 as score_fast computes them)
     for_each_wave_trial(
-        T, [&](int t) { return !flag && und_of(tC[t]) > 0 && cnt_of(tC[t]) + und_of(tC[t]) >= mlo; },
+        T, [&](int t) { return !flag && rec_und(t) > 0 && rec_cnt(t) + rec_und(t) >= mlo; },
         [&](int tc) {
           const Model m = fit_of(tc);
           int c = 0;
@@ -287,15 +344,12 @@ __device__ __forceinline__ void ransac_rigid_frame(
           c = wave_sum_i(c);
           double slo, shi;
           sd_bracket(wave_sum(sq), N, slo, shi);
+          outward(slo, shi);
           if (!(slo >= 1e-30 && shi <= 1e30)) flag = 1;
-          if (lane == 0) {
-            tC[tc] = c;
-            tS[tc] = slo;
-            tSh[tc] = shi;
-          }
+          if (lane == 0) rec_put(tc, c, slo, shi);
         });
     __syncthreads();  // the A2 results of the other waves' lanes
-    for (int t = tid; t < T; t += kThreads) mcount = max(mcount, cnt_of(tC[t]));
+    for (int t = tid; t < T; t += kThreads) mcount = max(mcount, rec_cnt(t));
   }
   block_max_flag(mcount, flag, sc.cnt);
   const bool exact = flag != 0 || mcount <= 0;
@@ -314,13 +368,13 @@ __device__ __forceinline__ void ransac_rigid_frame(
   } else {
     double lm = INFINITY;
     for (int t = tid; t < T; t += kThreads)
-      if (cnt_of(tC[t]) == mcount) lm = fmin(lm, tSh[t]);
+      if (rec_cnt(t) == mcount) lm = fmin(lm, rec_hi(t));
     const double minhi = block_min(lm, sc.min);
-    double* vals = wvals + wave * 128;
+    double* vals = wvals + wave * (LARGE ? 128 : N);
     double* wstk = stk + wave * kMaxStack;  // LARGE: the wave's combine stack (uniform values)
     // phase B: this wave's candidate trials, each scored by the whole wave
     for_each_wave_trial(
-        T, [&](int t) { return cnt_of(tC[t]) == mcount && tS[t] <= minhi; },
+        T, [&](int t) { return rec_cnt(t) == mcount && rec_lo(t) <= minhi; },
         [&](int tc) {
           const Model m = fit_of(tc);
           const double S = wave_pairwise<LARGE>(
@@ -437,9 +491,11 @@ __device__ __forceinline__ void ransac_rigid_frame(
   }
 }
 
-// One workgroup per frame.
+// One workgroup per frame.  The N <= 128 kernels are bounded at 5 waves per SIMD (96 VGPRs
+// allocated; 90 / 94 used, no scratch): a retiring warp tile leaves 120 VGPRs per SIMD free,
+// and under the bound of 4 the compiler spends 126 / 124.
 template <bool LARGE, bool SCALE>
-__global__ __launch_bounds__(kThreads, 4) void ransac_rigid_kernel(
+__global__ __launch_bounds__(kThreads, LARGE ? 4 : 5) void ransac_rigid_kernel(
     const double* __restrict__ src, const double* __restrict__ dst, const int32_t* __restrict__ pt_idx,
     const int32_t* __restrict__ pt_off, int src_stride, const uint32_t* __restrict__ hyp,
     const int32_t* __restrict__ hyp_off, int hyp_off_len,
@@ -448,6 +504,13 @@ __global__ __launch_bounds__(kThreads, 4) void ransac_rigid_kernel(
   ransac_rigid_frame<LARGE, SCALE>(blockIdx.x, src, dst, pt_idx, pt_off, src_stride, hyp, hyp_off, hyp_off_len, T, thresh,
                                    tq, rate, n_skip, out_params, out_inl, out_nin, out_best);
 }
+
+// The slot one retiring warp tile frees on a CU (warp.hip: 8 workgroups of 20,480 B): an
+// N <= 128 workgroup at the default 1000 trials fits it with its static LDS (the reduction
+// scratch, the bounding boxes and the selection flag, 224 B as compiled).  More trials keep
+// working; they only do not fit the slot.
+static_assert(rigid_small_lds(128, 1000) + sizeof(Scratch) + sizeof(Mag) + 16 <= 20480,
+              "the N <= 128 rigid RANSAC workgroup must fit one warp tile's LDS");
 
 }  // namespace
 }  // namespace kcmc
@@ -469,9 +532,8 @@ static int ransac_rigid_impl(kcmc_ctx* ctx, const double* src, const double* dst
                                  std::to_string(trials) + " (call kcmc_ransac_prepare)");
   const int n_small = need < 128 ? need : 128;
   const size_t wvals = (size_t)kThreads / 64 * 128 * sizeof(double);
-  // per point 4 f64 + one f32x4, per trial 2 f64 + one i32
-  const size_t lds_small = (size_t)n_small * (4 * sizeof(double) + 16) + (size_t)trials * (2 * sizeof(double) + sizeof(int)) +
-                           wvals + (size_t)n_small + 16;
+  // N <= 128: the compact layout; large: per point 4 f64 + one f32x4, per trial 2 f64 + one i32
+  const size_t lds_small = rigid_small_lds((size_t)n_small, (size_t)trials);
   const size_t lds_large = (size_t)need * (4 * sizeof(double) + 16) + (size_t)trials * (2 * sizeof(double) + sizeof(int)) +
                            (size_t)kMaxStack * kThreads * sizeof(double) + wvals + (size_t)need + 16;
   return launch_small_large(who, ransac_rigid_kernel<false, SCALE>, ransac_rigid_kernel<true, SCALE>, n_frames, max_n,

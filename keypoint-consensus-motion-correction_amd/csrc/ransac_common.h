@@ -257,6 +257,42 @@ __device__ __forceinline__ void sd_bracket(double Sd, int N, double& lo, double&
   hi = Sd * (1.0 + eps);
 }
 
+// ---------------------------------------------------------------- the rigid scorer's compact records
+// The N <= 128 rigid kernels keep a trial's bracket as two floats rounded outward (the low
+// bound toward -inf, the high bound toward +inf, as lin32_make directs its bounds) and its two
+// counts as bytes: 10 B per trial instead of 20, so that the workgroup's LDS fits the 20 KiB
+// slot a retiring warp tile leaves.  f32_below(d) is the largest float <= d,
+// f32_above(d) the smallest float >= d, for every finite d (beyond the float range: -inf /
+// -FLT_MAX and FLT_MAX / +inf); NaN stays NaN.  Plain C++ on bit patterns: the host computes
+// the same values.
+__host__ __device__ inline float f32_step(float f, bool up) {  // the next float above / below a finite f
+  int32_t i = __builtin_bit_cast(int32_t, f);
+  if (f == 0.f) return __builtin_bit_cast(float, up ? 0x00000001 : (int32_t)0x80000001);
+  i += ((f > 0.f) == up) ? 1 : -1;
+  return __builtin_bit_cast(float, i);
+}
+__host__ __device__ inline float f32_below(double d) {
+  const float f = (float)d;
+  return (double)f > d ? f32_step(f, false) : f;
+}
+__host__ __device__ inline float f32_above(double d) {
+  const float f = (float)d;
+  return (double)f < d ? f32_step(f, true) : f;
+}
+
+// A trial's counts as bytes (counts <= 128): kNoModel for a trial without a model, kDeferred
+// for one the fp32 bound cannot take (scored by the fp64 phase A); both read as count -1.
+constexpr uint8_t kNoModel = 255, kDeferred = 254;
+__host__ __device__ inline int cnt_of8(uint8_t c) { return c >= kDeferred ? -1 : (int)c; }
+// The dynamic LDS of an N <= 128 rigid workgroup with n points and T trials: the points as
+// f64 | a region shared by phase A's fp32 points (16 n) and phase B's leaf values (4 waves x
+// n f64), then the 10-byte records; the exact path's 12-byte records (S f64, count i32) lie
+// over both | the inlier flags | 16 bytes of slack.
+constexpr size_t rigid_small_lds(size_t n, size_t T) {
+  const size_t fast = 32 * n + 10 * T, exact = 12 * T;
+  return 32 * n + (fast > exact ? fast : exact) + n + 16;
+}
+
 // Phase A's per-trial record in the tC array: the certain inlier count and the undecided
 // points (cnt | und << 16, counts <= kMaxN < 2^16), -1 for a trial without a model.
 __device__ __forceinline__ int pack_cnt(int cnt, int und) { return cnt | (und << 16); }
@@ -509,8 +545,9 @@ struct Best {
 
 // Exact scoring of every trial, each by one thread (the frames phase A cannot decide):
 // score(t, cnt) returns numpy's S of trial t and adds its inliers to cnt, NaN for a trial
-// without a model.  Skipped trials (estimate() False) and NaN scores never win; with 0 inliers
-// a trial wins only with S < inf (skimage's strict comparisons against (0, inf)).
+// without a model.  Skipped trials (estimate() False) and NaN scores without inliers never win;
+// with 0 inliers a trial wins only with S < inf (skimage's strict comparisons against (0, inf)).
+// any_zero asks select_best for the sequential replay: some S <= 0, or a NaN S with inliers.
 template <class Score>
 __device__ __forceinline__ void exact_trials(int T, Score score, double* tS, int* tC, Best& best, bool& any_zero) {
   for (int t = threadIdx.x; t < T; t += kThreads) {
@@ -521,6 +558,11 @@ __device__ __forceinline__ void exact_trials(int T, Score score, double* tS, int
     if (!isnan(S) && (cnt > 0 || S < INFINITY)) {
       if (S <= 0.0) any_zero = true;
       best.take(cnt, S, t);
+    } else if (cnt > 0) {
+      // a model with inliers and S = NaN (a NaN coordinate elsewhere in the frame): skimage's
+      // comparisons take it on its count alone and nothing at that count replaces it, which is
+      // no order a reduction can follow: select_best replays the sequence
+      any_zero = true;
     }
   }
 }
@@ -542,7 +584,7 @@ __device__ __forceinline__ void for_each_wave_trial(int T, Pred pred, Body body)
 }
 
 // The selection's tail: workgroup argmax of (count, -S, -t) over every thread's best, and,
-// when an exactly scored trial had S <= 0, skimage's early exit from the trials' records
+// when an exactly scored trial had S <= 0 (or a NaN S with inliers), skimage's loop over the trials' records
 // tS / tC (s_any_zero: zero before the barrier that precedes the scoring).  best_t = -1 and
 // best_c = 0: no trial can be selected.
 __device__ __forceinline__ void select_best(Best b, bool any_zero, int T, const double* tS, const int* tC, Scratch& sc,
@@ -568,7 +610,8 @@ __device__ __forceinline__ void select_best(Best b, bool any_zero, int T, const 
       for (int t = 0; t < T; ++t) {
         const double S = tS[t];
         const int c = tC[t];
-        if (isnan(S)) continue;
+        // skimage's own comparisons: a trial without a model (S = NaN, no inliers) never
+        // passes them, one with inliers and S = NaN passes on its count
         if (c > c0 || (c == c0 && S < S0)) {
           c0 = c;
           S0 = S;

@@ -50,7 +50,7 @@ struct WarpCfg {
   static constexpr int kLdsElems = LDS_ELEMS;    // uint16 staging budget per box
   static constexpr int kRowPasses = ROW_PASSES;  // staging passes of 8 rows x 32 chunks
 };
-using BlockCfg = WarpCfg<56, kLdsElems, kRowPasses>;  // 20 KB box, box rows <= 72 (7 workgroups per CU)
+using BlockCfg = WarpCfg<56, kLdsElems, kRowPasses>;  // 20 KB box, box rows <= 72 (8 workgroups per CU: all 160 KiB of LDS)
 // use_tile64 frames: 64-row tiles with the same 20 KB box budget cover them exactly (the
 // fast path's 71 staged rows still hold a 64-row tile rotated by up to ~2.5 deg; larger
 // rotations take the general staged path or the direct gather).
