@@ -76,48 +76,174 @@ __device__ __forceinline__ Model fit2(double sx0, double sy0, double sx1, double
   return m;
 }
 
-struct Pts {
-  const double* sx;
-  const double* sy;
-  const double* dx;
-  const double* dy;
-};
-
-__device__ __forceinline__ double resid2(const Model& m, const Pts& P, int k, double thresh, int& cnt) {
-  const double x = P.sx[k], y = P.sy[k];
+// The squared residual distance of point (x, y) -> (u, v) under m.  Every phase that compares q
+// with tq or sums it calls this, so their q is resid2's to the bit.
+__device__ __forceinline__ double q_of(const Model& m, double x, double y, double u, double v) {
   const double xp = fma(y, -m.s, x * m.c) + m.tx;
   const double yp = fma(y, m.c, x * m.s) + m.ty;
-  const double ex = xp - P.dx[k], ey = yp - P.dy[k];
-  const double r = sqrt_resid(ex * ex + ey * ey);
+  const double ex = xp - u, ey = yp - v;
+  return ex * ex + ey * ey;
+}
+
+__device__ __forceinline__ double resid2(const Model& m, const Pts& P, int k, double thresh, int& cnt) {
+  const double r = sqrt_resid(q_of(m, P.sx[k], P.sy[k], P.dx[k], P.dy[k]));
   cnt += (r < thresh) ? 1 : 0;
   return r * r;
 }
 
-// Phase A of the scoring (see the kernel): the inlier count through the squared
+// Phase A of the scoring (see the kernel) in fp64: the inlier count through the squared
 // distance (r < thresh <=> q < tq, tq = the smallest double whose correctly rounded root
-// is >= thresh; the q of every point is computed exactly as resid2 computes it) and an
-// fp32 estimate of S = sum r_k^2: sum_k (float)q_k in sequence.  r_k^2 = q_k (1 + d),
-// |d| <= 3 2^-53, numpy's pairwise sum adds <= N 2^-53 and the fp32 sum of N
-// conversions <= (N + 1) 2^-24, so for S32 >= 1e-30 (no fp32 underflow matters)
+// is >= thresh) and an fp32 estimate of S = sum r_k^2: sum_k (float)q_k in sequence.
+// r_k^2 = q_k (1 + d), |d| <= 3 2^-53, numpy's pairwise sum adds <= N 2^-53 and the fp32 sum
+// of N conversions <= (N + 1) 2^-24, so for S32 >= 1e-30 (no fp32 underflow matters)
 // |S - S32| <= (N + 2) 2^-23 S32, used with a 2x margin.
 __device__ __forceinline__ float score_fast(const Model& m, const Pts& P, int N, double tq, int& cnt) {
   float S = 0.f;
   for (int k = 0; k < N; ++k) {
-    const double x = P.sx[k], y = P.sy[k];
-    const double xp = fma(y, -m.s, x * m.c) + m.tx;
-    const double yp = fma(y, m.c, x * m.s) + m.ty;
-    const double ex = xp - P.dx[k], ey = yp - P.dy[k];
-    const double q = ex * ex + ey * ey;
+    const double q = q_of(m, P.sx[k], P.sy[k], P.dx[k], P.dy[k]);
     cnt += (q < tq) ? 1 : 0;
     S += (float)q;
   }
   return S;
 }
 
-// For N > 128 the numpy pairwise order comes from the per-frame split Plan
-// (ransac_common.h); invalid trials (NaN S, or 0 inliers with S = inf) never win.
-// LARGE = false handles frames with N <= 128 (one pairwise leaf, fully in registers)
-// and the NaN frames; LARGE = true handles 128 < N <= kMaxN through the split plan.
+// Staging: the points (gather(k, c): point k as (x, y, u, v)) to sx .. dy, the frame's boxes
+// to mg and the centred fp32 copies to pk32; ends behind a barrier.
+template <bool LARGE, class Gather>
+__device__ __forceinline__ void stage_points(Gather gather, int N, double* sx, double* sy, double* dx, double* dy,
+                                             float4* pk32, double* red, Mag& mg) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  if constexpr (LARGE) {
+    for (int k = tid; k < N; k += kThreads) {
+      double c[4];
+      gather(k, c);
+      sx[k] = c[0];
+      sy[k] = c[1];
+      dx[k] = c[2];
+      dy[k] = c[3];
+    }
+    __syncthreads();
+    frame_mag(sx, sy, dx, dy, N, red, mg);
+    for (int k = tid; k < N; k += kThreads) pk32[k] = centred32(sx[k], sy[k], dx[k], dy[k], mg);
+  } else if (tid < 64) {
+    // N <= 128: wave 0 stages every point (k = lane, lane + 64), takes the frame's boxes by
+    // wave reductions (min / max: the same bounds in any order) and writes the fp32 copies,
+    // behind one barrier (the workgroup form takes five)
+    double c[2][4], lo[4] = {INFINITY, INFINITY, INFINITY, INFINITY}, hi[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+    bool bad = false;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int k = lane + 64 * h;
+      if (k < N) {
+        gather(k, c[h]);
+        mag_add(c[h], lo, hi, bad);
+      }
+    }
+    wave_bounds(lo, hi, bad);
+    const Mag m = mag_of(lo, hi);
+    if (lane == 0) mg = m;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int k = lane + 64 * h;
+      if (k < N) {
+        sx[k] = c[h][0];
+        sy[k] = c[h][1];
+        dx[k] = c[h][2];
+        dy[k] = c[h][3];
+        pk32[k] = centred32(c[h][0], c[h][1], c[h][2], c[h][3], m);
+      }
+    }
+  }
+  __syncthreads();
+}
+
+// The refit's sums (skimage fit.py:871-875 -> _umeyama over d[best_inliers]): the inliers' number,
+// means of (x, y) and (u, v), un-normalised covariance and, SCALE, variance sum of (x, y).
+struct Umeyama {
+  double n_in, ms0, ms1, md0, md1, a00 = 0, a01 = 0, a10 = 0, a11 = 0, vs = 0;
+};
+
+template <bool LARGE, bool SCALE>
+__device__ __forceinline__ Umeyama umeyama_sums(const Pts& P, const uint8_t* inl, int N, double* red) {
+  Umeyama u;
+  const int tid = threadIdx.x, lane = tid & 63;
+  if constexpr (!LARGE) {
+    // N <= 128: wave 0 alone (the caller's), with no barrier.  Lane l holds points l and l + 64,
+    // the points threads l and l + 64 hold in the workgroup form below; each half goes through
+    // the same butterfly as there, and the halves are added as block_sum adds its four wave
+    // sums (0 + wave 0 + wave 1 + 0 + 0), so every sum is the same to the bit.
+    const int k1 = lane + 64;
+    const bool i0 = lane < N && inl[lane], i1 = k1 < N && inl[k1];
+    auto half_sums = [&](double lo, double hi) {
+      for (int o = 32; o > 0; o >>= 1) {
+        lo += __shfl_xor(lo, o);
+        hi += __shfl_xor(hi, o);
+      }
+      return (((0.0 + lo) + hi) + 0.0) + 0.0;
+    };
+    u.n_in = half_sums(i0 ? 1.0 : 0.0, i1 ? 1.0 : 0.0);
+    u.ms0 = half_sums(i0 ? 0.0 + P.sx[lane] : 0.0, i1 ? 0.0 + P.sx[k1] : 0.0) / u.n_in;
+    u.ms1 = half_sums(i0 ? 0.0 + P.sy[lane] : 0.0, i1 ? 0.0 + P.sy[k1] : 0.0) / u.n_in;
+    u.md0 = half_sums(i0 ? 0.0 + P.dx[lane] : 0.0, i1 ? 0.0 + P.dx[k1] : 0.0) / u.n_in;
+    u.md1 = half_sums(i0 ? 0.0 + P.dy[lane] : 0.0, i1 ? 0.0 + P.dy[k1] : 0.0) / u.n_in;
+    double b[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, bv[2] = {0, 0};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int k = h ? k1 : lane;
+      if (h ? i1 : i0) {
+        const double u0 = P.sx[k] - u.ms0, u1 = P.sy[k] - u.ms1;
+        const double v0 = P.dx[k] - u.md0, v1 = P.dy[k] - u.md1;
+        b[h][0] = 0.0 + v0 * u0;
+        b[h][1] = 0.0 + v0 * u1;
+        b[h][2] = 0.0 + v1 * u0;
+        b[h][3] = 0.0 + v1 * u1;
+        if (SCALE) bv[h] = 0.0 + (u0 * u0 + u1 * u1);
+      }
+    }
+    u.a00 = half_sums(b[0][0], b[1][0]);
+    u.a01 = half_sums(b[0][1], b[1][1]);
+    u.a10 = half_sums(b[0][2], b[1][2]);
+    u.a11 = half_sums(b[0][3], b[1][3]);
+    if (SCALE) u.vs = half_sums(bv[0], bv[1]);
+  } else {
+    double s0 = 0, s1 = 0, s2 = 0, s3 = 0, cntd = 0;
+    for (int k = tid; k < N; k += kThreads)
+      if (inl[k]) {
+        s0 += P.sx[k];
+        s1 += P.sy[k];
+        s2 += P.dx[k];
+        s3 += P.dy[k];
+        cntd += 1.0;
+      }
+    u.n_in = block_sum(cntd, red);
+    u.ms0 = block_sum(s0, red) / u.n_in;
+    u.ms1 = block_sum(s1, red) / u.n_in;
+    u.md0 = block_sum(s2, red) / u.n_in;
+    u.md1 = block_sum(s3, red) / u.n_in;
+    for (int k = tid; k < N; k += kThreads)
+      if (inl[k]) {
+        const double u0 = P.sx[k] - u.ms0, u1 = P.sy[k] - u.ms1;
+        const double v0 = P.dx[k] - u.md0, v1 = P.dy[k] - u.md1;
+        u.a00 += v0 * u0;
+        u.a01 += v0 * u1;
+        u.a10 += v1 * u0;
+        u.a11 += v1 * u1;
+        if (SCALE) u.vs += u0 * u0 + u1 * u1;
+      }
+    u.a00 = block_sum(u.a00, red);
+    u.a01 = block_sum(u.a01, red);
+    u.a10 = block_sum(u.a10, red);
+    u.a11 = block_sum(u.a11, red);
+    if (SCALE) u.vs = block_sum(u.vs, red);
+  }
+  return u;
+}
+
+// One frame: begin, stage, phase A, A2, B or exact, select, mask, refit.  The LDS is
+// RigidSmallLds / RigidLargeLds (ransac_common.h).  For N > 128 the numpy pairwise order
+// comes from the per-frame split Plan; invalid trials (NaN S, or 0 inliers with S = inf)
+// never win.  LARGE = false handles frames with N <= 128 (one pairwise leaf, fully in
+// registers) and the NaN frames; LARGE = true handles 128 < N <= kMaxN through the split plan.
 template <bool LARGE, bool SCALE>
 __device__ __forceinline__ void ransac_rigid_frame(
     int f, const double* __restrict__ src, const double* __restrict__ dst, const int32_t* __restrict__ pt_idx,
@@ -130,6 +256,7 @@ __device__ __forceinline__ void ransac_rigid_frame(
   __shared__ Scratch sc;
   __shared__ int s_any_zero;
   __shared__ Plan s_plan;
+  __shared__ Mag mg;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
@@ -139,79 +266,17 @@ __device__ __forceinline__ void ransac_rigid_frame(
     return;
   const uint32_t* H = hyp + hoff;
 
-  // LDS, LARGE: sx, sy, dx, dy [N] f64 | the points as (x, y, u, v) [N] f32x4 | trial S (low
-  //      bound) [T] f64 | trial S high bound [T] f64 | stack [kMaxStack][256] f64 | per-wave
-  //      leaf values [4][128] f64 | trial count [T] i32 | inlier flags [N] u8
-  // N <= 128 (ransac_common.h rigid_small_lds; at N = 128, T = 1000 the workgroup takes 18,336
-  // B of dynamic LDS, inside the 20 KiB a retiring warp tile frees): sx, sy, dx, dy [N] f64 |
-  //      a region that holds the f32x4 points in phase A and the per-wave leaf values [4][N]
-  //      f64 in phase B (phase A is the only reader of the fp32 points, phase B the only
-  //      writer of the leaf values, barriers between) | a trial's bracket as two floats
-  //      rounded outward [T] f32 x 2 | certain count, undecided count [T] u8 x 2 | inlier
-  //      flags [N] u8.  The exact path's records (S [T] f64, count [T] i32) lie over the
-  //      region and the compact records: it starts behind a barrier after the last read of both.
-  // Outward rounding keeps every bracket a bound on numpy's S: lo' <= lo <= S <= hi <= hi'.
-  // The trial with the smallest S at the best count, S*, has lo'* <= S* <= S_t <= hi'_t for
-  // every trial t at that count, so it -- and every trial that ties it -- stays a phase-B
-  // candidate (lo' <= min hi'); phase B scores each candidate exactly and selects on the exact
-  // values, so wider brackets add candidates and change no output.  The brackets' validity
-  // tests (1e-30 .. 1e30, which also send every S == 0 to the exact path) see the rounded values.
-  double* sx = smem;
-  double* sy = sx + N;
-  double* dxs = sy + N;
-  double* dys = dxs + N;
-  float4* pk32 = reinterpret_cast<float4*>(dys + N);  // 16-byte aligned: 4 N doubles before it
-  double* tS = reinterpret_cast<double*>(pk32 + (LARGE ? N : 0));
-  double* tSh = tS + T;  // LARGE only
-  double* stk = tSh + T;
-  double* wvals = LARGE ? stk + kMaxStack * kThreads : tS;
-  int* tC = reinterpret_cast<int*>(LARGE ? wvals + kThreads / 64 * 128 : tS + T);
-  float* fLo = reinterpret_cast<float*>(tS + 4 * N);  // N <= 128 only, and the three below
-  float* fHi = fLo + T;
-  uint8_t* bC = reinterpret_cast<uint8_t*>(fHi + T);
-  uint8_t* bU = bC + T;
-  uint8_t* inl = LARGE ? reinterpret_cast<uint8_t*>(tC + T)
-                       : reinterpret_cast<uint8_t*>(tS) + max(32 * N + 10 * T, 12 * T);
-  // a trial's phase-A record: v = pack_cnt(certain, undecided), -1 (no model) or INT_MIN
-  // (deferred to the fp64 phase A), and the bracket of its S
-  auto rec_put = [&](int t, int v, double slo, double shi) {
-    if constexpr (LARGE) {
-      tC[t] = v;
-      tS[t] = slo;
-      tSh[t] = shi;
-    } else {
-      bC[t] = v == INT_MIN ? kDeferred : v < 0 ? kNoModel : (uint8_t)(v & 0xffff);
-      bU[t] = (uint8_t)und_of(v);
-      fLo[t] = (float)slo;  // exact: outward() rounded both
-      fHi[t] = (float)shi;
-    }
-  };
-  auto outward = [&](double& slo, double& shi) {
-    if constexpr (!LARGE) {
-      slo = (double)f32_below(slo);
-      shi = (double)f32_above(shi);
-    }
-  };
-  auto rec_cnt = [&](int t) {
-    if constexpr (LARGE) return cnt_of(tC[t]);
-    else return cnt_of8(bC[t]);
-  };
-  auto rec_und = [&](int t) {
-    if constexpr (LARGE) return und_of(tC[t]);
-    else return bC[t] >= kDeferred ? 0 : (int)bU[t];
-  };
-  auto rec_deferred = [&](int t) {
-    if constexpr (LARGE) return tC[t] == INT_MIN;
-    else return bC[t] == kDeferred;
-  };
-  auto rec_lo = [&](int t) {
-    if constexpr (LARGE) return tS[t];
-    else return (double)fLo[t];
-  };
-  auto rec_hi = [&](int t) {
-    if constexpr (LARGE) return tSh[t];
-    else return (double)fHi[t];
-  };
+  const RigidLds<LARGE> lds((size_t)N, (size_t)T);
+  double *sx = lds_at<double>(smem, lds.sx), *sy = lds_at<double>(smem, lds.sy);
+  double *dxs = lds_at<double>(smem, lds.dx), *dys = lds_at<double>(smem, lds.dy);
+  float4* pk32 = lds_at<float4>(smem, lds.pk32);
+  double* wvals = lds_at<double>(smem, lds.wvals);
+  double* tS = lds_at<double>(smem, lds.tS);  // tS, tC: the exact path's records
+  int* tC = lds_at<int>(smem, lds.tC);
+  uint8_t* inl = lds_at<uint8_t>(smem, lds.inl);
+  double* stk = nullptr;  // the combine stacks, LARGE only
+  if constexpr (LARGE) stk = lds_at<double>(smem, lds.stk);
+  const Records<LARGE> rec(smem, lds);  // phase A's records
   if (LARGE && tid == 0) {
     s_plan.n = 0;
     plan_gen<kPwDepth>(s_plan, 0, N);
@@ -221,52 +286,7 @@ __device__ __forceinline__ void ransac_rigid_frame(
     gather_point(src, dst, pt_idx, src_stride, f, p0 + k, c[0], c[1], c[2], c[3]);
   };
   if (tid == 0) s_any_zero = 0;
-  __shared__ Mag mg;
-  if (!LARGE) {
-    // N <= 128: wave 0 stages every point (k = lane, lane + 64), takes the frame's boxes by
-    // wave reductions (min / max: the same bounds in any order) and writes the fp32 copies,
-    // behind one barrier (the workgroup form takes five)
-    if (wave == 0) {
-      double c[2][4], lo[4] = {INFINITY, INFINITY, INFINITY, INFINITY}, hi[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-      bool bad = false;
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int k = lane + 64 * h;
-        if (k < N) {
-          gather(k, c[h]);
-          mag_add(c[h], lo, hi, bad);
-        }
-      }
-      wave_bounds(lo, hi, bad);
-      const Mag m = mag_of(lo, hi);
-      if (lane == 0) mg = m;
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int k = lane + 64 * h;
-        if (k < N) {
-          sx[k] = c[h][0];
-          sy[k] = c[h][1];
-          dxs[k] = c[h][2];
-          dys[k] = c[h][3];
-          pk32[k] = centred32(c[h][0], c[h][1], c[h][2], c[h][3], m);
-        }
-      }
-    }
-    __syncthreads();
-  } else {
-    for (int k = tid; k < N; k += kThreads) {
-      double c[4];
-      gather(k, c);
-      sx[k] = c[0];
-      sy[k] = c[1];
-      dxs[k] = c[2];
-      dys[k] = c[3];
-    }
-    __syncthreads();
-    frame_mag(sx, sy, dxs, dys, N, red, mg);
-    for (int k = tid; k < N; k += kThreads) pk32[k] = centred32(sx[k], sy[k], dxs[k], dys[k], mg);
-    __syncthreads();
-  }
+  stage_points<LARGE>(gather, N, sx, sy, dxs, dys, pk32, red, mg);
 
   const Pts P{sx, sy, dxs, dys};
   auto fit_of = [&](int t) {  // trial t's model from its sample pair
@@ -275,7 +295,7 @@ __device__ __forceinline__ void ransac_rigid_frame(
     return fit2<SCALE>(sx[i], sy[i], sx[j], sy[j], dxs[i], dys[i], dxs[j], dys[j]);
   };
 
-  // ---- phase A: every trial's inlier count and a bracket [tS, tSh] of its S.  In fp32
+  // ---- phase A: every trial's inlier count and a bracket of its S, in rec.  In fp32
   // (ransac_common.h score32: certain inliers, outliers and the undecided points between
   // them; a trial whose map or frame is too large for the fp32 bound runs the fp64 form,
   // score_fast).  A trial whose undecided points could lift it to the best certain count
@@ -298,27 +318,27 @@ __device__ __forceinline__ void ransac_rigid_frame(
         int clo = 0, chi = 0;
         const float S32 = score32(pk32, N, L, clo, chi);
         s32_bracket(S32, N, L.be, slo, shi);
-        outward(slo, shi);
+        rec.outward(slo, shi);
         v = pack_cnt(clo, chi - clo);
         if (!(slo >= 1e-30 && shi <= 1e30)) flag = 1;
       } else if (m.ok) {
         v = INT_MIN;
         deferred = true;
       }
-      rec_put(t, v, slo, shi);
+      rec.put(t, v, slo, shi);
       mlo = max(mlo, cnt_of(v));
     }
     if (deferred) {
       for (int t = tid; t < T; t += kThreads) {
-        if (!rec_deferred(t)) continue;
+        if (!rec.deferred(t)) continue;
         const Model m = fit_of(t);
         int cnt = 0;
         const float S32 = score_fast(m, P, N, tq, cnt);
         double slo, shi;
         s64_bracket(S32, N, slo, shi);
-        outward(slo, shi);
+        rec.outward(slo, shi);
         if (!(slo >= 1e-30 && shi <= 1e30)) flag = 1;
-        rec_put(t, cnt, slo, shi);
+        rec.put(t, cnt, slo, shi);
         mlo = max(mlo, cnt);
       }
     }
@@ -327,29 +347,25 @@ __device__ __forceinline__ void ransac_rigid_frame(
     // phase A2: the exact count of every trial the undecided points could lift to mlo, each
     // by a whole wave (the points over the lanes, fp64 as score_fast computes them)
     for_each_wave_trial(
-        T, [&](int t) { return !flag && rec_und(t) > 0 && rec_cnt(t) + rec_und(t) >= mlo; },
+        T, [&](int t) { return !flag && rec.und(t) > 0 && rec.cnt(t) + rec.und(t) >= mlo; },
         [&](int tc) {
           const Model m = fit_of(tc);
           int c = 0;
           double sq = 0.0;
           for (int k = lane; k < N; k += 64) {
-            const double x = sx[k], y = sy[k];
-            const double xp = fma(y, -m.s, x * m.c) + m.tx;
-            const double yp = fma(y, m.c, x * m.s) + m.ty;
-            const double ex = xp - dxs[k], ey = yp - dys[k];
-            const double q = ex * ex + ey * ey;
+            const double q = q_of(m, P.sx[k], P.sy[k], P.dx[k], P.dy[k]);
             c += (q < tq) ? 1 : 0;
             sq += q;
           }
           c = wave_sum_i(c);
           double slo, shi;
           sd_bracket(wave_sum(sq), N, slo, shi);
-          outward(slo, shi);
+          rec.outward(slo, shi);
           if (!(slo >= 1e-30 && shi <= 1e30)) flag = 1;
-          if (lane == 0) rec_put(tc, c, slo, shi);
+          if (lane == 0) rec.put(tc, c, slo, shi);
         });
     __syncthreads();  // the A2 results of the other waves' lanes
-    for (int t = tid; t < T; t += kThreads) mcount = max(mcount, rec_cnt(t));
+    for (int t = tid; t < T; t += kThreads) mcount = max(mcount, rec.cnt(t));
   }
   block_max_flag(mcount, flag, sc.cnt);
   const bool exact = flag != 0 || mcount <= 0;
@@ -368,13 +384,13 @@ __device__ __forceinline__ void ransac_rigid_frame(
   } else {
     double lm = INFINITY;
     for (int t = tid; t < T; t += kThreads)
-      if (rec_cnt(t) == mcount) lm = fmin(lm, rec_hi(t));
+      if (rec.cnt(t) == mcount) lm = fmin(lm, rec.hi(t));
     const double minhi = block_min(lm, sc.min);
     double* vals = wvals + wave * (LARGE ? 128 : N);
     double* wstk = stk + wave * kMaxStack;  // LARGE: the wave's combine stack (uniform values)
     // phase B: this wave's candidate trials, each scored by the whole wave
     for_each_wave_trial(
-        T, [&](int t) { return rec_cnt(t) == mcount && rec_lo(t) <= minhi; },
+        T, [&](int t) { return rec.cnt(t) == mcount && rec.lo(t) <= minhi; },
         [&](int tc) {
           const Model m = fit_of(tc);
           const double S = wave_pairwise<LARGE>(
@@ -399,94 +415,25 @@ __device__ __forceinline__ void ransac_rigid_frame(
     out_inl[p0 + k] = (uint8_t)c;
   }
   __syncthreads();
-  // refit on the inliers (skimage fit.py:871-875 -> _umeyama over d[best_inliers])
-  double n_in, ms0, ms1, md0, md1, a00 = 0, a01 = 0, a10 = 0, a11 = 0, vs = 0;
-  if (!LARGE) {
-    // N <= 128: wave 0 alone, with no barrier.  Lane l holds points l and l + 64, the
-    // points threads l and l + 64 hold in the workgroup form below; each half goes through
-    // the same butterfly as there, and the halves are added as block_sum adds its four wave
-    // sums (0 + wave 0 + wave 1 + 0 + 0), so every sum is the same to the bit.
-    if (wave != 0) return;
-    const int k1 = lane + 64;
-    const bool i0 = lane < N && inl[lane], i1 = k1 < N && inl[k1];
-    auto half_sums = [&](double lo, double hi) {
-      for (int o = 32; o > 0; o >>= 1) {
-        lo += __shfl_xor(lo, o);
-        hi += __shfl_xor(hi, o);
-      }
-      return (((0.0 + lo) + hi) + 0.0) + 0.0;
-    };
-    n_in = half_sums(i0 ? 1.0 : 0.0, i1 ? 1.0 : 0.0);
-    ms0 = half_sums(i0 ? 0.0 + sx[lane] : 0.0, i1 ? 0.0 + sx[k1] : 0.0) / n_in;
-    ms1 = half_sums(i0 ? 0.0 + sy[lane] : 0.0, i1 ? 0.0 + sy[k1] : 0.0) / n_in;
-    md0 = half_sums(i0 ? 0.0 + dxs[lane] : 0.0, i1 ? 0.0 + dxs[k1] : 0.0) / n_in;
-    md1 = half_sums(i0 ? 0.0 + dys[lane] : 0.0, i1 ? 0.0 + dys[k1] : 0.0) / n_in;
-    double b[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}}, bv[2] = {0, 0};
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int k = h ? k1 : lane;
-      if (h ? i1 : i0) {
-        const double u0 = sx[k] - ms0, u1 = sy[k] - ms1;
-        const double v0 = dxs[k] - md0, v1 = dys[k] - md1;
-        b[h][0] = 0.0 + v0 * u0;
-        b[h][1] = 0.0 + v0 * u1;
-        b[h][2] = 0.0 + v1 * u0;
-        b[h][3] = 0.0 + v1 * u1;
-        if (SCALE) bv[h] = 0.0 + (u0 * u0 + u1 * u1);
-      }
-    }
-    a00 = half_sums(b[0][0], b[1][0]);
-    a01 = half_sums(b[0][1], b[1][1]);
-    a10 = half_sums(b[0][2], b[1][2]);
-    a11 = half_sums(b[0][3], b[1][3]);
-    if (SCALE) vs = half_sums(bv[0], bv[1]);
-  } else {
-    double s0 = 0, s1 = 0, s2 = 0, s3 = 0, cntd = 0;
-    for (int k = tid; k < N; k += kThreads)
-      if (inl[k]) {
-        s0 += sx[k];
-        s1 += sy[k];
-        s2 += dxs[k];
-        s3 += dys[k];
-        cntd += 1.0;
-      }
-    n_in = block_sum(cntd, red);
-    ms0 = block_sum(s0, red) / n_in;
-    ms1 = block_sum(s1, red) / n_in;
-    md0 = block_sum(s2, red) / n_in;
-    md1 = block_sum(s3, red) / n_in;
-    for (int k = tid; k < N; k += kThreads)
-      if (inl[k]) {
-        const double u0 = sx[k] - ms0, u1 = sy[k] - ms1;
-        const double v0 = dxs[k] - md0, v1 = dys[k] - md1;
-        a00 += v0 * u0;
-        a01 += v0 * u1;
-        a10 += v1 * u0;
-        a11 += v1 * u1;
-        if (SCALE) vs += u0 * u0 + u1 * u1;
-      }
-    a00 = block_sum(a00, red);
-    a01 = block_sum(a01, red);
-    a10 = block_sum(a10, red);
-    a11 = block_sum(a11, red);
-    if (SCALE) vs = block_sum(vs, red);
-  }
+  // refit on the inliers: wave 0 alone for N <= 128
+  if (!LARGE && wave != 0) return;
+  const Umeyama u = umeyama_sums<LARGE, SCALE>(P, inl, N, red);
   if (tid == 0) {
     double* o = out_params + 6 * (size_t)f;
-    const double a = a00 + a11, b = a10 - a01;
-    if (n_in > 0.0 && !(a == 0.0 && b == 0.0)) {
-      const double hn = SCALE ? vs : sqrt(a * a + b * b);
+    const double a = u.a00 + u.a11, b = u.a10 - u.a01;
+    if (u.n_in > 0.0 && !(a == 0.0 && b == 0.0)) {
+      const double hn = SCALE ? u.vs : sqrt(a * a + b * b);
       const double c = a / hn, s = b / hn;
       o[0] = c;
       o[1] = -s;
-      o[2] = (md0 - (c * ms0 - s * ms1)) * rate;
+      o[2] = (u.md0 - (c * u.ms0 - s * u.ms1)) * rate;
       o[3] = s;
       o[4] = c;
-      o[5] = (md1 - (s * ms0 + c * ms1)) * rate;
+      o[5] = (u.md1 - (s * u.ms0 + c * u.ms1)) * rate;
     } else {
       for (int k = 0; k < 6; ++k) o[k] = NAN;
     }
-    out_nin[f] = (int32_t)n_in;
+    out_nin[f] = (int32_t)u.n_in;
     out_best[f] = best_t;
   }
 }
@@ -509,7 +456,7 @@ __global__ __launch_bounds__(kThreads, LARGE ? 4 : 5) void ransac_rigid_kernel(
 // N <= 128 workgroup at the default 1000 trials fits it with its static LDS (the reduction
 // scratch, the bounding boxes and the selection flag, 224 B as compiled).  More trials keep
 // working; they only do not fit the slot.
-static_assert(rigid_small_lds(128, 1000) + sizeof(Scratch) + sizeof(Mag) + 16 <= 20480,
+static_assert(RigidSmallLds(128, 1000).bytes() + sizeof(Scratch) + sizeof(Mag) + 16 <= 20480,
               "the N <= 128 rigid RANSAC workgroup must fit one warp tile's LDS");
 
 }  // namespace
@@ -526,20 +473,13 @@ static int ransac_rigid_impl(kcmc_ctx* ctx, const double* src, const double* dst
   const int rc = check_ransac_args(who, ctx, src, dst, pt_idx, pt_off, src_frame_stride, n_frames, max_n, trials,
                                    out_params, out_inliers, out_n_inliers, out_best_trial);
   if (rc != KCMC_OK || n_frames == 0) return rc;
-  const int need = max_n < 3 ? 3 : max_n;
   if (!ctx->hyp || ctx->hyp_trials != trials)
     return fail(KCMC_EINVAL, std::string(who) + "hypothesis tables not prepared for trials=" +
                                  std::to_string(trials) + " (call kcmc_ransac_prepare)");
-  const int n_small = need < 128 ? need : 128;
-  const size_t wvals = (size_t)kThreads / 64 * 128 * sizeof(double);
-  // N <= 128: the compact layout; large: per point 4 f64 + one f32x4, per trial 2 f64 + one i32
-  const size_t lds_small = rigid_small_lds((size_t)n_small, (size_t)trials);
-  const size_t lds_large = (size_t)need * (4 * sizeof(double) + 16) + (size_t)trials * (2 * sizeof(double) + sizeof(int)) +
-                           (size_t)kMaxStack * kThreads * sizeof(double) + wvals + (size_t)need + 16;
-  return launch_small_large(who, ransac_rigid_kernel<false, SCALE>, ransac_rigid_kernel<true, SCALE>, n_frames, max_n,
-                            lds_small, lds_large, (hipStream_t)stream, src, dst, pt_idx, pt_off, src_frame_stride,
-                            ctx->hyp, ctx->hyp_off, ctx->hyp_off_len, trials, thresh, inlier_bound(thresh), rate, n_skip,
-                            out_params, out_inliers, out_n_inliers, out_best_trial);
+  return launch_small_large<RigidSmallLds, RigidLargeLds>(
+      who, ransac_rigid_kernel<false, SCALE>, ransac_rigid_kernel<true, SCALE>, n_frames, max_n, 3, trials,
+      (hipStream_t)stream, src, dst, pt_idx, pt_off, src_frame_stride, ctx->hyp, ctx->hyp_off, ctx->hyp_off_len, trials,
+      thresh, inlier_bound(thresh), rate, n_skip, out_params, out_inliers, out_n_inliers, out_best_trial);
 }
 
 extern "C" int kcmc_ransac_rigid(kcmc_ctx* ctx, const double* src, const double* dst, const int32_t* pt_idx,

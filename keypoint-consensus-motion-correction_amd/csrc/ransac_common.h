@@ -7,6 +7,7 @@
 #include <climits>
 #include <cmath>
 #include <cstdint>
+#include <type_traits>
 
 #include "kcmc_internal.h"
 
@@ -50,6 +51,67 @@ __device__ __forceinline__ void plan_gen(Plan& p, int s, int n) {
     ++p.pops[p.n - 1];
   }
 }
+
+// ---------------------------------------------------------------- the workgroups' dynamic LDS
+// One description per workgroup kind, built from (n points, T trials): the byte offset of every
+// region.  The kernel takes its pointers from it with the frame's own N (lds_at), the launcher
+// its size with the launch's largest n; bytes() does not decrease in n.  Every kind starts with
+// the staged points sx, sy, dx, dy [n] f64 (Pts: (x, y) of the frame, (dx, dy) of the template).
+constexpr size_t kStackBytes = kMaxStack * kThreads * sizeof(double);   // thread_pairwise's stacks
+constexpr size_t kLeafBytes = kThreads / 64 * 128 * sizeof(double);     // wave_leaf's rows, [4][128] f64
+
+struct Pts {
+  const double *sx, *sy, *dx, *dy;
+};
+
+template <class T>
+__device__ __forceinline__ T* lds_at(double* smem, size_t off) {
+  return reinterpret_cast<T*>(reinterpret_cast<char*>(smem) + off);
+}
+
+// Rigid / similarity, N <= 128: exactly 64 n + max(10 T, 12 T - 32 n) + n + 16 bytes (18,336 at
+// (128, 1000): with the static LDS inside the 20 KiB slot a retiring warp tile leaves, DESIGN
+// 4, K2).  Two overlays, each side used behind a barrier after the last access of the other:
+//   pk32 = wvals: phase A is the only reader of the centred fp32 points ([n] float4), phase B
+//     the only writer of the per-wave leaf values ([4][n] f64);
+//   tS, tC: the exact path's records (S [T] f64, count [T] i32) lie over that region and the
+//     compact 10-byte records (a trial's bracket as two floats rounded outward lo, hi [T] f32,
+//     its certain and undecided counts cnt, und [T] u8, see Records).
+struct RigidSmallLds {
+  size_t sx, sy, dx, dy, pk32, wvals, lo, hi, cnt, und, tS, tC, inl, end;
+  __host__ __device__ constexpr RigidSmallLds(size_t n, size_t T)
+      : sx(0), sy(8 * n), dx(16 * n), dy(24 * n), pk32(32 * n), wvals(pk32), lo(wvals + 32 * n), hi(lo + 4 * T),
+        cnt(hi + 4 * T), und(cnt + T), tS(pk32), tC(tS + 8 * T),
+        inl(und + T > tC + 4 * T ? und + T : tC + 4 * T), end(inl + n) {}  // inl: the inlier flags [n] u8
+  __host__ __device__ constexpr size_t bytes() const { return end + 16; }  // the slot argument's figure
+};
+constexpr size_t rigid_small_lds(size_t n, size_t T) { return RigidSmallLds(n, T).bytes(); }
+
+// Rigid / similarity, 128 < N <= kMaxN: the fp32 points [n] float4 | a trial's bracket lo, hi
+// [T] f64 | the threads' combine stacks | the waves' leaf values | a trial's counts cnt [T] i32
+// (pack_cnt) | the inlier flags [n] u8.  The exact path's tS and tC are lo and cnt.
+struct RigidLargeLds {
+  size_t sx, sy, dx, dy, pk32, lo, hi, stk, wvals, cnt, tS, tC, inl, end;
+  __host__ __device__ constexpr RigidLargeLds(size_t n, size_t T)
+      : sx(0), sy(8 * n), dx(16 * n), dy(24 * n), pk32(32 * n), lo(pk32 + 16 * n), hi(lo + 8 * T), stk(hi + 8 * T),
+        wvals(stk + kStackBytes), cnt(wvals + kLeafBytes), tS(lo), tC(cnt), inl(cnt + 4 * T), end(inl + n) {}
+  __host__ __device__ constexpr size_t bytes() const { return end; }
+};
+template <bool LARGE>
+using RigidLds = std::conditional_t<LARGE, RigidLargeLds, RigidSmallLds>;
+
+// Affine / projective, N <= 128 (LARGE = false) and 128 < N <= kMaxN: the points again as (x, y,
+// dx, dy) for phase A, pk [n] of 32 B (ransac_model.hip PackedPt; N <= 128 only) | trial S [T]
+// f64 | the threads' combine stacks (LARGE only: N <= 128 is one pairwise leaf) | the waves'
+// leaf values | trial count [T] i32 | the winner's inlier mask [n] u8 (the fused refit's).
+template <bool LARGE>
+struct ModelLds {
+  size_t sx, sy, dx, dy, pk, tS, stk, wvals, tC, inl, end;
+  __host__ __device__ constexpr ModelLds(size_t n, size_t T)
+      : sx(0), sy(8 * n), dx(16 * n), dy(24 * n), pk(32 * n), tS(pk + (LARGE ? 0 : 32 * n)), stk(tS + 8 * T),
+        wvals(stk + (LARGE ? kStackBytes : 0)), tC(wvals + kLeafBytes), inl(tC + 4 * T), end(inl + n) {}
+  __host__ __device__ constexpr size_t bytes() const { return end; }
+};
 
 // sqrt of a squared residual distance, the hot op of every scoring loop: the same
 // rsq + Goldschmidt/Newton sequence (and so the same correctly rounded result) that
@@ -142,9 +204,8 @@ __device__ __forceinline__ double wave_pairwise(R2 r2, int N, const Plan& plan, 
 // Phase A's error bound (the kernels' comment): |S - S32| <= eps S32 for S32 in
 // [1e-30, 1e30], with a 2x margin.
 __device__ __forceinline__ double s32_eps(int N) { return (double)(N + 2) * 0x1p-22; }
-__device__ __forceinline__ bool s32_certain(float S32) { return S32 >= 1e-30f && S32 <= 1e30f; }
-// The same for a sequential fp64 sum Sd of the q (the model scorers' phase A): numpy's S is
-// within (N + 3) 2^-53 S of the exact sum of the q, Sd within (N - 1) 2^-53 (2x margin); the
+// The same for an fp64 sum Sd of the q (the model scorers' phase A): numpy's S is within
+// (N + 3) 2^-53 S of the exact sum of the q, Sd in any order within (N - 1) 2^-53 (2x margin); the
 // range excludes every S == 0 (skimage's early exit) and the under / overflowing sums.
 __device__ __forceinline__ double sd_eps(int N) { return (double)(2 * N + 8) * 0x1p-52; }
 __device__ __forceinline__ bool sd_certain(double Sd) { return Sd >= 1e-290 && Sd <= 1e290; }
@@ -249,10 +310,9 @@ __device__ __forceinline__ void s64_bracket(float S32, int N, double& lo, double
   hi = (double)S32 * (1.0 + eps);
 }
 
-// The bracket of a wave's fp64 sum Sd of the q (phase A2): numpy's S is within
-// (N + 3) 2^-53 S of the sum of the q, any summation order within (N - 1) 2^-53 (2x margin).
+// The bracket of a wave's fp64 sum Sd of the q (phase A2; sd_eps holds for any summation order).
 __device__ __forceinline__ void sd_bracket(double Sd, int N, double& lo, double& hi) {
-  const double eps = (double)(2 * N + 8) * 0x1p-52;
+  const double eps = sd_eps(N);
   lo = Sd * (1.0 - eps);
   hi = Sd * (1.0 + eps);
 }
@@ -260,8 +320,7 @@ __device__ __forceinline__ void sd_bracket(double Sd, int N, double& lo, double&
 // ---------------------------------------------------------------- the rigid scorer's compact records
 // The N <= 128 rigid kernels keep a trial's bracket as two floats rounded outward (the low
 // bound toward -inf, the high bound toward +inf, as lin32_make directs its bounds) and its two
-// counts as bytes: 10 B per trial instead of 20, so that the workgroup's LDS fits the 20 KiB
-// slot a retiring warp tile leaves.  f32_below(d) is the largest float <= d,
+// counts as bytes (Records<false> in RigidSmallLds).  f32_below(d) is the largest float <= d,
 // f32_above(d) the smallest float >= d, for every finite d (beyond the float range: -inf /
 // -FLT_MAX and FLT_MAX / +inf); NaN stays NaN.  Plain C++ on bit patterns: the host computes
 // the same values.
@@ -284,20 +343,55 @@ __host__ __device__ inline float f32_above(double d) {
 // for one the fp32 bound cannot take (scored by the fp64 phase A); both read as count -1.
 constexpr uint8_t kNoModel = 255, kDeferred = 254;
 __host__ __device__ inline int cnt_of8(uint8_t c) { return c >= kDeferred ? -1 : (int)c; }
-// The dynamic LDS of an N <= 128 rigid workgroup with n points and T trials: the points as
-// f64 | a region shared by phase A's fp32 points (16 n) and phase B's leaf values (4 waves x
-// n f64), then the 10-byte records; the exact path's 12-byte records (S f64, count i32) lie
-// over both | the inlier flags | 16 bytes of slack.
-constexpr size_t rigid_small_lds(size_t n, size_t T) {
-  const size_t fast = 32 * n + 10 * T, exact = 12 * T;
-  return 32 * n + (fast > exact ? fast : exact) + n + 16;
-}
 
 // Phase A's per-trial record in the tC array: the certain inlier count and the undecided
 // points (cnt | und << 16, counts <= kMaxN < 2^16), -1 for a trial without a model.
 __device__ __forceinline__ int pack_cnt(int cnt, int und) { return cnt | (und << 16); }
 __device__ __forceinline__ int cnt_of(int v) { return v < 0 ? v : (v & 0xffff); }
 __device__ __forceinline__ int und_of(int v) { return v < 0 ? 0 : (v >> 16); }
+
+// The rigid kernels' phase-A records, 20 B per trial (LARGE) or the compact 10 B.  put(t, v, slo,
+// shi): v = pack_cnt(certain, undecided), -1 (no model) or INT_MIN (deferred to the fp64 phase
+// A), and the bracket of S, which outward() has rounded to what the format keeps.  Outward
+// rounding keeps every bracket a bound on numpy's S: lo' <= lo <= S <= hi <= hi'.  The trial with
+// the smallest S at the best count, S*, has lo'* <= S* <= S_t <= hi'_t for every trial t at that
+// count, so it -- and every trial that ties it -- stays a phase-B candidate (lo' <= min hi');
+// phase B scores each candidate exactly and selects on the exact values, so wider brackets add
+// candidates and change no output.  The brackets' validity tests (1e-30 .. 1e30, which also send
+// every S == 0 to the exact path) see the rounded values.
+template <bool LARGE>
+struct Records {
+  using Bound = std::conditional_t<LARGE, double, float>;
+  using Count = std::conditional_t<LARGE, int, uint8_t>;
+  Bound *blo, *bhi;
+  Count* c;
+  uint8_t* u = nullptr;  // the undecided counts, !LARGE only
+  __device__ Records(double* smem, const RigidLds<LARGE>& L)
+      : blo(lds_at<Bound>(smem, L.lo)), bhi(lds_at<Bound>(smem, L.hi)), c(lds_at<Count>(smem, L.cnt)) {
+    if constexpr (!LARGE) u = lds_at<uint8_t>(smem, L.und);
+  }
+  __device__ static void outward(double& slo, double& shi) {
+    if constexpr (!LARGE) {
+      slo = (double)f32_below(slo);
+      shi = (double)f32_above(shi);
+    }
+  }
+  __device__ void put(int t, int v, double slo, double shi) const {
+    if constexpr (LARGE) {
+      c[t] = v;
+    } else {
+      c[t] = v == INT_MIN ? kDeferred : v < 0 ? kNoModel : (uint8_t)(v & 0xffff);
+      u[t] = (uint8_t)und_of(v);
+    }
+    blo[t] = (Bound)slo;  // exact: outward() rounded both
+    bhi[t] = (Bound)shi;
+  }
+  __device__ int cnt(int t) const { return LARGE ? cnt_of(c[t]) : cnt_of8((uint8_t)c[t]); }
+  __device__ int und(int t) const { return LARGE ? und_of(c[t]) : c[t] >= kDeferred ? 0 : (int)u[t]; }
+  __device__ bool deferred(int t) const { return c[t] == (LARGE ? INT_MIN : (int)kDeferred); }
+  __device__ double lo(int t) const { return (double)blo[t]; }
+  __device__ double hi(int t) const { return (double)bhi[t]; }
+};
 
 __device__ __forceinline__ int wave_sum_i(int v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
@@ -650,10 +744,14 @@ inline int check_ransac_args(const char* who, const kcmc_ctx* ctx, const double*
 
 // One workgroup per frame: the small kernel (frames with N <= 128 and the NaN frames) and, when
 // a frame can have more points, the large one (narrower grids measured slower beside the warp,
-// DESIGN 6d).
-template <class... P, class... A>
+// DESIGN 6d).  Each launch's dynamic LDS is its layout's (SmallLds, LargeLds) at the launch's
+// largest frame: max_n, at least the model's min_n, and at most 128 for the small kernel.
+template <class SmallLds, class LargeLds, class... P, class... A>
 inline int launch_small_large(const char* who, void (*small)(P...), void (*large)(P...), int n_frames, int max_n,
-                              size_t lds_small, size_t lds_large, hipStream_t s, A... args) {
+                              int min_n, int trials, hipStream_t s, A... args) {
+  const size_t need = max_n < min_n ? min_n : max_n;
+  const size_t lds_small = SmallLds(need < 128 ? need : 128, (size_t)trials).bytes();
+  const size_t lds_large = LargeLds(need, (size_t)trials).bytes();
   if ((max_n > 128 ? lds_large : lds_small) > 150 * 1024)
     return fail(KCMC_EUNSUPPORTED, std::string(who) + "max_n/trials exceed the LDS budget");
   hipLaunchKernelGGL(small, dim3((unsigned)n_frames), dim3(kThreads), lds_small, s, args...);

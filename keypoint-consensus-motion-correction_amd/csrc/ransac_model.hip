@@ -52,13 +52,6 @@ struct HModel {
   bool ok;
 };
 
-struct Pts {
-  const double* sx;
-  const double* sy;
-  const double* dx;
-  const double* dy;
-};
-
 // skimage _center_and_normalize_points for the K sample points: centroid = numpy's
 // sequential axis-0 mean, rms = sqrt(pairwise_sum of the 2K squared deviations / K)
 // (2K < 8: sequential; 2K == 8: numpy's 8-accumulator combine).  false: rms == 0.
@@ -335,9 +328,11 @@ __device__ __forceinline__ HModel projective_fit4(const Pts& P, const int (&sel)
   return m;
 }
 
+// The squared residual distance of point (x, y) -> (u, v) under h, as _apply_mat maps it
+// ([x y 1] @ H^T in the dgemm operation order; w == 0 -> eps; divide).  Every phase that
+// compares q with tq or sums it calls this, so their q is resid2's to the bit.
 template <int MODEL>
-__device__ __forceinline__ double resid2(const double (&h)[9], const Pts& P, int k, double thresh, int& cnt) {
-  const double x = P.sx[k], y = P.sy[k];
+__device__ __forceinline__ double q_of(const double (&h)[9], double x, double y, double u, double v) {
   double X = fma(y, h[1], x * h[0]) + h[2];
   double Y = fma(y, h[4], x * h[3]) + h[5];
   if (MODEL == KCMC_MODEL_PROJECTIVE) {
@@ -346,32 +341,26 @@ __device__ __forceinline__ double resid2(const double (&h)[9], const Pts& P, int
     X = X / w;
     Y = Y / w;
   }
-  const double ex = X - P.dx[k], ey = Y - P.dy[k];
-  const double r = sqrt_resid(ex * ex + ey * ey);
+  const double ex = X - u, ey = Y - v;
+  return ex * ex + ey * ey;
+}
+
+template <int MODEL>
+__device__ __forceinline__ double resid2(const double (&h)[9], const Pts& P, int k, double thresh, int& cnt) {
+  const double r = sqrt_resid(q_of<MODEL>(h, P.sx[k], P.sy[k], P.dx[k], P.dy[k]));
   cnt += (r < thresh) ? 1 : 0;
   return r * r;
 }
 
 // Phase A of the scoring (the rigid kernel's, ransac.hip): the exact inlier count through
-// q < tq (q computed as resid2 computes it) and the estimate Sd = sum q_k, summed in
-// sequence in fp64 (round 6; was an fp32 sum of (float)q_k): within sd_eps(N) of numpy's S,
-// so phase B re-scores only trials tied to ~1e-14 instead of ~1e-5 (one fp64 add per point
-// in place of a conversion and an fp32 add).
+// q < tq and the estimate Sd = sum q_k, summed in sequence in fp64 (round 6; was an fp32 sum
+// of (float)q_k): within sd_eps(N) of numpy's S, so phase B re-scores only trials tied to
+// ~1e-14 instead of ~1e-5 (one fp64 add per point in place of a conversion and an fp32 add).
 template <int MODEL>
 __device__ __forceinline__ double score_fast(const double (&h)[9], const Pts& P, int N, double tq, int& cnt) {
   double S = 0.0;
   for (int k = 0; k < N; ++k) {
-    const double x = P.sx[k], y = P.sy[k];
-    double X = fma(y, h[1], x * h[0]) + h[2];
-    double Y = fma(y, h[4], x * h[3]) + h[5];
-    if (MODEL == KCMC_MODEL_PROJECTIVE) {
-      double w = fma(y, h[7], x * h[6]) + h[8];
-      if (w == 0.0) w = DBL_EPSILON;
-      X = X / w;
-      Y = Y / w;
-    }
-    const double ex = X - P.dx[k], ey = Y - P.dy[k];
-    const double q = ex * ex + ey * ey;
+    const double q = q_of<MODEL>(h, P.sx[k], P.sy[k], P.dx[k], P.dy[k]);
     cnt += (q < tq) ? 1 : 0;
     S += q;
   }
@@ -391,16 +380,7 @@ __device__ __forceinline__ double score_fast_packed(const double (&h)[9], const 
                                                     double tq, int& cnt) {
   double S = 0.0;
   auto one = [&](const PackedPt p) {
-    double X = fma(p.s.y, h[1], p.s.x * h[0]) + h[2];
-    double Y = fma(p.s.y, h[4], p.s.x * h[3]) + h[5];
-    if (MODEL == KCMC_MODEL_PROJECTIVE) {
-      double w = fma(p.s.y, h[7], p.s.x * h[6]) + h[8];
-      if (w == 0.0) w = DBL_EPSILON;
-      X = X / w;
-      Y = Y / w;
-    }
-    const double ex = X - p.d.x, ey = Y - p.d.y;
-    const double q = ex * ex + ey * ey;
+    const double q = q_of<MODEL>(h, p.s.x, p.s.y, p.d.x, p.d.y);
     cnt += (q < tq) ? 1 : 0;
     S += q;
   };
@@ -414,30 +394,32 @@ __device__ __forceinline__ double score_fast_packed(const double (&h)[9], const 
   return S;
 }
 
-// Phase A's fit: affine through affine_fit3_fast (need_exact: the trial must be fitted
-// again by fit_trial), projective as fit_trial.
-template <int MODEL>
-__device__ __forceinline__ HModel fit_trial_fast(const Pts& P, uint64_t pr, bool& need_exact) {
-  if constexpr (MODEL == KCMC_MODEL_AFFINE) {
-    const int sel[3] = {(int)(pr & 0xffffu), (int)((pr >> 16) & 0xffffu), (int)((pr >> 32) & 0xffffu)};
-    return affine_fit3_fast(P, sel, need_exact);
-  } else {
-    need_exact = false;
-    const int sel[4] = {(int)(pr & 0xffffu), (int)((pr >> 16) & 0xffffu), (int)((pr >> 32) & 0xffffu),
-                        (int)((pr >> 48) & 0xffffu)};
-    return projective_fit4(P, sel);
-  }
+// A trial's sample: K point indices of 16 bits each, the first in the low bits.
+template <int K>
+__device__ __forceinline__ void unpack_sample(uint64_t pr, int (&sel)[K]) {
+#pragma unroll
+  for (int i = 0; i < K; ++i) sel[i] = (int)((pr >> (16 * i)) & 0xffffu);
 }
 
 template <int MODEL>
 __device__ __forceinline__ HModel fit_trial(const Pts& P, uint64_t pr) {
+  int sel[MODEL == KCMC_MODEL_AFFINE ? 3 : 4];
+  unpack_sample(pr, sel);
+  if constexpr (MODEL == KCMC_MODEL_AFFINE) return affine_fit3(P, sel);
+  else return projective_fit4(P, sel);
+}
+
+// Phase A's fit: affine through affine_fit3_fast (need_exact: the trial must be fitted
+// again by fit_trial), projective as fit_trial.
+template <int MODEL>
+__device__ __forceinline__ HModel fit_trial_fast(const Pts& P, uint64_t pr, bool& need_exact) {
+  need_exact = false;
   if constexpr (MODEL == KCMC_MODEL_AFFINE) {
-    const int sel[3] = {(int)(pr & 0xffffu), (int)((pr >> 16) & 0xffffu), (int)((pr >> 32) & 0xffffu)};
-    return affine_fit3(P, sel);
+    int sel[3];
+    unpack_sample(pr, sel);
+    return affine_fit3_fast(P, sel, need_exact);
   } else {
-    const int sel[4] = {(int)(pr & 0xffffu), (int)((pr >> 16) & 0xffffu), (int)((pr >> 32) & 0xffffu),
-                        (int)((pr >> 48) & 0xffffu)};
-    return projective_fit4(P, sel);
+    return fit_trial<MODEL>(P, pr);
   }
 }
 
@@ -473,19 +455,15 @@ __device__ __forceinline__ void ransac_model_score_frame(
                              N, hoff))
     return;
 
-  // LDS: sx, sy, dx, dy [N] f64 | trial S [T] f64 | [LARGE: stack [kMaxStack][256] f64]
-  //      | per-wave leaf values [4][128] f64 | trial count [T] i32 | the winner's inlier mask [N] u8
-  double* sx = smem;
-  double* sy = sx + N;
-  double* dxs = sy + N;
-  double* dys = dxs + N;
-  // !LARGE: the points again as (x, y, dx, dy) for phase A (16-byte aligned: smem is)
-  PackedPt* pk = reinterpret_cast<PackedPt*>(smem + ((4 * N + 1) & ~1));
-  double* tS = LARGE ? dys + N : reinterpret_cast<double*>(pk + N);
-  double* stk = tS + T;
-  double* wvals = stk + (LARGE ? kMaxStack * kThreads : 0);
-  int* tC = reinterpret_cast<int*>(wvals + kThreads / 64 * 128);
-  uint8_t* sinl = reinterpret_cast<uint8_t*>(tC + T);
+  const ModelLds<LARGE> lds((size_t)N, (size_t)T);  // ransac_common.h: every region of the LDS
+  double *sx = lds_at<double>(smem, lds.sx), *sy = lds_at<double>(smem, lds.sy);
+  double *dxs = lds_at<double>(smem, lds.dx), *dys = lds_at<double>(smem, lds.dy);
+  PackedPt* pk = lds_at<PackedPt>(smem, lds.pk);  // !LARGE only
+  double* tS = lds_at<double>(smem, lds.tS);
+  double* stk = lds_at<double>(smem, lds.stk);  // LARGE only
+  double* wvals = lds_at<double>(smem, lds.wvals);
+  int* tC = lds_at<int>(smem, lds.tC);
+  uint8_t* sinl = lds_at<uint8_t>(smem, lds.inl);
   if (LARGE && tid == 0) {
     s_plan.n = 0;
     plan_gen<kPwDepth>(s_plan, 0, N);
@@ -507,10 +485,8 @@ __device__ __forceinline__ void ransac_model_score_frame(
   const bool fast = tq == tq;
   int mcount = -1, flag = fast ? 0 : 1;
   if (fast) {
-    bool deferred = false;
-    for (int t = tid; t < T; t += kThreads) {
-      bool need_exact;
-      const HModel m = fit_trial_fast<MODEL>(P, H[t], need_exact);
+    // trial t's record from its model m; need_exact (m is then no model): marked for the pass below
+    auto phase_a = [&](int t, const HModel& m, bool need_exact) {
       int cnt = -1;
       double Sd = NAN;
       if (m.ok) {
@@ -518,28 +494,21 @@ __device__ __forceinline__ void ransac_model_score_frame(
         Sd = LARGE ? score_fast<MODEL>(m.h, P, N, tq, cnt) : score_fast_packed<MODEL>(m.h, pk, N, tq, cnt);
         if (!sd_certain(Sd)) flag = 1;
       }
-      deferred |= need_exact;
       tC[t] = need_exact ? INT_MIN : cnt;
       tS[t] = Sd;
       mcount = max(mcount, cnt);
+    };
+    bool deferred = false;
+    for (int t = tid; t < T; t += kThreads) {
+      bool need_exact;
+      const HModel m = fit_trial_fast<MODEL>(P, H[t], need_exact);
+      phase_a(t, m, need_exact);
+      deferred |= need_exact;
     }
     // trials whose fast fit fell outside its ranges (in practice none): the reference fit
-    if (deferred) {
-      for (int t = tid; t < T; t += kThreads) {
-        if (tC[t] != INT_MIN) continue;
-        const HModel m = fit_trial<MODEL>(P, H[t]);
-        int cnt = -1;
-        double Sd = NAN;
-        if (m.ok) {
-          cnt = 0;
-          Sd = LARGE ? score_fast<MODEL>(m.h, P, N, tq, cnt) : score_fast_packed<MODEL>(m.h, pk, N, tq, cnt);
-          if (!sd_certain(Sd)) flag = 1;
-        }
-        tC[t] = cnt;
-        tS[t] = Sd;
-        mcount = max(mcount, cnt);
-      }
-    }
+    if (deferred)
+      for (int t = tid; t < T; t += kThreads)
+        if (tC[t] == INT_MIN) phase_a(t, fit_trial<MODEL>(P, H[t]), false);
   }
   block_max_flag(mcount, flag, sc.cnt);
   const bool exact = flag != 0 || mcount <= 0;
@@ -986,7 +955,6 @@ __device__ __forceinline__ void refit_frame(int N, int lane, PointFn point, Inli
   }
 }
 
-
 }  // namespace
 }  // namespace kcmc
 
@@ -1011,23 +979,16 @@ extern "C" int kcmc_ransac_model(kcmc_ctx* ctx, int model, const double* src, co
     return fail(KCMC_EINVAL, "kcmc_ransac_model: hypothesis tables not prepared for min_samples=" +
                                  std::to_string(ms) + ", trials=" + std::to_string(trials) +
                                  " (call kcmc_ransac_prepare_samples)");
-  const int need = max_n < ms + 1 ? ms + 1 : max_n;
-  const int n_small = need < 128 ? need : 128;
-  const size_t wvals = (size_t)kThreads / 64 * 128 * sizeof(double);
-  // + the winner's inlier mask (N bytes) for the fused refit
-  const size_t lds_small = (size_t)(n_small + 1) * 4 * sizeof(double) + (size_t)n_small * 4 * sizeof(double) +
-                           (size_t)trials * (sizeof(double) + sizeof(int)) + wvals + 16 + (((size_t)n_small + 15) & ~15);
-  const size_t lds_large = (size_t)need * 4 * sizeof(double) + (size_t)trials * (sizeof(double) + sizeof(int)) + wvals +
-                           (size_t)kMaxStack * kThreads * sizeof(double) + 16 + (((size_t)need + 15) & ~15);
   hipStream_t s = (hipStream_t)stream;
   // The scoring kernel writes out_params: the homography's refit is fused into it (one wave
   // per frame, points and mask from LDS); the affine model's hypothesis model goes there
   // first and ransac_model_refit_kernel overwrites it with the refit.  No workspace: a
   // stream-ordered pool allocation cost ~0.2 ms of host time per call.
   auto score = [&](auto small, auto large) {
-    return launch_small_large(who, small, large, n_frames, max_n, lds_small, lds_large, s, src, dst, pt_idx, pt_off,
-                              src_frame_stride, tab.dev, tab.off, tab.off_len, trials, thresh, inlier_bound(thresh),
-                              n_skip, rate, out_params, out_inliers, out_n_inliers, out_best_trial);
+    return launch_small_large<ModelLds<false>, ModelLds<true>>(
+        who, small, large, n_frames, max_n, ms + 1, trials, s, src, dst, pt_idx, pt_off, src_frame_stride, tab.dev,
+        tab.off, tab.off_len, trials, thresh, inlier_bound(thresh), n_skip, rate, out_params, out_inliers, out_n_inliers,
+        out_best_trial);
   };
   if (model == KCMC_MODEL_PROJECTIVE)
     return score(ransac_model_score_kernel<KCMC_MODEL_PROJECTIVE, false>,

@@ -85,6 +85,23 @@ def test_ransac_model_bit_exact_selection_vs_oracle(dev, model):
 
 
 @pytest.mark.parametrize("model", MODELS)
+def test_ransac_model_each_point_count_in_a_launch_of_its_own(dev, model):
+    """One frame per launch, so the launch's dynamic LDS is sized for exactly that frame's count
+    (the kernel and its launcher take the layout from ransac_common.h ModelLds): the smallest
+    frame RANSAC runs on, both sides of the 128-point split and counts that are no multiple of
+    8 or 16, 1000 trials each."""
+    ms = 3 if model == "affine" else 4
+    Ns = [ms + 1, 8, 64, 127, 128, 129, 136, 257]
+    tpls, qs = _frames(np.random.default_rng(75 if model == "affine" else 76), model, Ns)
+    for tpl, q in zip(tpls, qs):
+        _, params, inl, nin, best = _run(dev, model, [tpl], [q], trials=1000)
+        p, i_ref, bt, ni = oracle.ransac_model(q, tpl, model, trials=1000)
+        assert best[0] == bt and nin[0] == ni, (len(q), best[0], bt, nin[0], ni)
+        assert np.array_equal(inl, i_ref), len(q)
+        np.testing.assert_allclose(params[0], p, rtol=1e-8, atol=1e-9, equal_nan=True, err_msg=str(len(q)))
+
+
+@pytest.mark.parametrize("model", MODELS)
 @pytest.mark.parametrize("thresh", [2.0, 1e-120, 5e-5])
 def test_ransac_model_two_phase_ties_and_exact_fallback(dev, model, thresh):
     """The two-phase scoring (counts through q < tq and fp32 S estimates, then numpy's

@@ -100,6 +100,16 @@ def test_large_path_untouched_at_129_points_37_trials(dev, model):
 
 
 @pytest.mark.parametrize("model", sorted(MODELS))
+def test_large_path_point_counts_each_alone(dev, model):
+    """129, 136 and 257 points at 1000 trials, every count in a launch of its own: max_n = N
+    sizes the large kernel's LDS (ransac_common.h RigidLargeLds) for exactly that frame."""
+    rng = np.random.default_rng(47)
+    for N in (129, 136, 257):
+        tpl, q = _noisy_frame(rng, N, rng.uniform(0.5, 2.0) if model == "similarity" else None)
+        assert _check(model, [tpl], [q], _run(dev, model, [tpl], [q]), ctx=(model, "large alone", N)) == 1
+
+
+@pytest.mark.parametrize("model", sorted(MODELS))
 def test_skipped_frame_and_nan_point(dev, model):
     """A frame below n_skip between two scored ones, and a frame with one NaN coordinate (its
     bounding boxes are infinite, every trial's S is NaN: the frame takes the exact path, where

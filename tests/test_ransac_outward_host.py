@@ -2,8 +2,10 @@
 a trial's bracket of S kept as two floats) on the host: a small program compiled from the
 header prints both roundings of every probe, and numpy checks each against its definition --
 f32_below(d) is the largest float <= d, f32_above(d) the smallest float >= d -- so a bracket
-stays a bound after the rounding.  Also the byte encoding of the counts and the LDS formula
-(ransac_common.h rigid_small_lds) at the sizes the slot argument names.  No GPU."""
+stays a bound after the rounding.  Also the byte encoding of the counts, the LDS formula
+(ransac_common.h rigid_small_lds) at the sizes the slot argument names, and the four LDS
+layouts the kernels and their launchers share (RigidSmallLds, RigidLargeLds, ModelLds): the
+program prints every region, this file says what each region holds.  No GPU."""
 import os
 import shutil
 import subprocess
@@ -15,9 +17,68 @@ CSRC = os.path.join(REPO, "keypoint-consensus-motion-correction_amd", "csrc")
 PROGRAM = r"""
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 #include "ransac_common.h"
 using namespace kcmc::ransac_common;
+// one line per region: layout, n, T, name, offset, then its size and alignment as the kernels
+// use it (what ransac.hip / ransac_model.hip keep there), and the layout's bytes()
+#define REGION(name, size, align) \
+  std::printf("%s %zu %zu %s %zu %zu %d\n", kind, n, T, #name, l.name, (size_t)(size), align)
+#define POINTS_AND_BYTES()                                                                    \
+  REGION(sx, 8 * n, 8); REGION(sy, 8 * n, 8); REGION(dx, 8 * n, 8); REGION(dy, 8 * n, 8); \
+  std::printf("%s %zu %zu bytes %zu 0 1\n", kind, n, T, l.bytes())
+constexpr size_t kStacks = kMaxStack * kThreads * 8, kLeaves = 4 * 128 * 8;  // f64 [kMaxStack][256], [4][128]
+void rigid_small(size_t n, size_t T) {
+  const char* kind = "rigid_small";
+  const RigidSmallLds l(n, T);
+  POINTS_AND_BYTES();
+  REGION(pk32, 16 * n, 16);    // float4 [n]
+  REGION(wvals, 4 * 8 * n, 8);  // f64 [4][n]
+  REGION(lo, 4 * T, 4);         // f32 [T]
+  REGION(hi, 4 * T, 4);
+  REGION(cnt, T, 1);            // u8 [T]
+  REGION(und, T, 1);
+  REGION(tS, 8 * T, 8);         // f64 [T]
+  REGION(tC, 4 * T, 4);         // i32 [T]
+  REGION(inl, n, 1);            // u8 [n]
+}
+void rigid_large(size_t n, size_t T) {
+  const char* kind = "rigid_large";
+  const RigidLargeLds l(n, T);
+  POINTS_AND_BYTES();
+  REGION(pk32, 16 * n, 16);
+  REGION(lo, 8 * T, 8);         // f64 [T]
+  REGION(hi, 8 * T, 8);
+  REGION(stk, kStacks, 8);
+  REGION(wvals, kLeaves, 8);
+  REGION(cnt, 4 * T, 4);        // i32 [T]
+  REGION(tS, 8 * T, 8);
+  REGION(tC, 4 * T, 4);
+  REGION(inl, n, 1);
+}
+template <bool LARGE>
+void model(size_t n, size_t T) {
+  const char* kind = LARGE ? "model_large" : "model_small";
+  const ModelLds<LARGE> l(n, T);
+  POINTS_AND_BYTES();
+  REGION(pk, LARGE ? 0 : 32 * n, 16);  // PackedPt [n], N <= 128 only
+  REGION(tS, 8 * T, 8);
+  REGION(stk, LARGE ? kStacks : 0, 8);  // N > 128 only
+  REGION(wvals, kLeaves, 8);
+  REGION(tC, 4 * T, 4);
+  REGION(inl, n, 1);
+}
+void layouts() {
+  for (size_t T : {1, 37, 1000}) {
+    for (size_t n : {3, 5, 64, 127, 128}) rigid_small(n, T), model<false>(n, T);
+    for (size_t n : {129, 136, 1024, 4096}) rigid_large(n, T), model<true>(n, T);
+  }
+}
 int main(int argc, char** argv) {
+  if (argc == 2 && std::string(argv[1]) == "layouts") {
+    layouts();
+    return 0;
+  }
   if (argc == 1) {
     std::printf("%zu %zu %zu %d %d %d %d\n", rigid_small_lds(128, 1000), rigid_small_lds(100, 1000), rigid_small_lds(3, 1000),
                 cnt_of8(0), cnt_of8(128), cnt_of8(kNoModel), cnt_of8(kDeferred));
@@ -77,3 +138,53 @@ def test_outward_rounding_counts_and_lds_formula(tmp_path):
     assert v[:3] == [32 * 128 + 32 * 128 + 10000 + 128 + 16, 32 * 100 + 32 * 100 + 10000 + 100 + 16, 96 + 12000 + 3 + 16]
     assert v[0] + 224 <= 20480
     assert v[3:] == [0, 128, -1, -1]
+
+
+# The regions that lie over one another by design (ransac_common.h RigidSmallLds: phase A's fp32
+# points and phase B's leaf values share a region, the exact path's records lie over it and the
+# compact records; RigidLargeLds: the exact path's S and counts are phase A's low bounds and counts).
+OVERLAYS = {"rigid_small": [{"pk32", "wvals"}, {"tS", "pk32"}, {"tS", "wvals"}, {"tS", "lo"}, {"tS", "hi"}, {"tS", "cnt"},
+                            {"tS", "und"}, {"tC", "pk32"}, {"tC", "wvals"}, {"tC", "lo"}, {"tC", "hi"}, {"tC", "cnt"},
+                            {"tC", "und"}],
+            "rigid_large": [{"tS", "lo"}, {"tC", "cnt"}], "model_small": [], "model_large": []}
+# the parent commit's launch formulas: rigid small is held exactly, the others may only shrink
+FORMULAS = {"rigid_small": lambda n, T: 64 * n + max(10 * T, 12 * T - 32 * n) + n + 16,
+            "rigid_large": lambda n, T: 49 * n + 20 * T + 20496,
+            "model_small": lambda n, T: 64 * n + 12 * T + 4144 + (n + 15) // 16 * 16,
+            "model_large": lambda n, T: 32 * n + 12 * T + 20496 + (n + 15) // 16 * 16}
+
+
+def test_lds_layouts_regions_alignment_and_sizes(tmp_path):
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    src, exe = tmp_path / "outward.cpp", tmp_path / "outward"
+    src.write_text(PROGRAM)
+    subprocess.run([hipcc, "-x", "hip", "--offload-host-only", "-O1", "-std=c++17", f"-I{CSRC}",
+                    f"-I{os.path.join(REPO, 'include')}", str(src), "-o", str(exe)], check=True, timeout=300)
+    out = subprocess.run([str(exe), "layouts"], check=True, capture_output=True, text=True, timeout=60).stdout
+    layouts = {}  # (kind, n, T) -> {region: (offset, size, alignment)}
+    for line in out.splitlines():
+        kind, n, T, name, off, size, align = line.split()
+        layouts.setdefault((kind, int(n), int(T)), {})[name] = (int(off), int(size), int(align))
+    small, large, Ts = [3, 5, 64, 127, 128], [129, 136, 1024, 4096], [1, 37, 1000]
+    assert sorted(layouts) == sorted([(k, n, T) for k, ns in (("rigid_small", small), ("model_small", small),
+                                                              ("rigid_large", large), ("model_large", large))
+                                      for n in ns for T in Ts])
+    expect = {"rigid_small": 14, "rigid_large": 14, "model_small": 11, "model_large": 11}  # regions + bytes
+    for (kind, n, T), regions in layouts.items():
+        total = regions.pop("bytes")[0]
+        assert len(regions) + 1 == expect[kind], (kind, sorted(regions))
+        for name, (off, size, align) in regions.items():
+            assert off % align == 0, (kind, n, T, name, off, align)  # f64: 8, float4 / PackedPt: 16
+            assert off + size <= total, (kind, n, T, name, off, size, total)
+        names = sorted(regions)
+        for i, a in enumerate(names):
+            for b in names[i + 1:]:
+                (oa, sa, _), (ob, sb, _) = regions[a], regions[b]
+                if {a, b} not in OVERLAYS[kind]:
+                    assert oa + sa <= ob or ob + sb <= oa, (kind, n, T, a, regions[a], b, regions[b])
+        assert total == FORMULAS[kind](n, T) if kind == "rigid_small" else total <= FORMULAS[kind](n, T), (kind, n, T, total)
+        layouts[(kind, n, T)] = total
+    for kind, ns in (("rigid_small", small), ("model_small", small), ("rigid_large", large), ("model_large", large)):
+        for T in Ts:  # a frame with N <= max_n fits the launch sized for max_n
+            sizes = [layouts[(kind, n, T)] for n in ns]
+            assert sizes == sorted(sizes), (kind, T, sizes)

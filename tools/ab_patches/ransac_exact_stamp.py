@@ -11,6 +11,6 @@ import sys
 
 path = os.path.join(sys.argv[1], "ransac.hip")
 src = open(path).read()
-old = "out_nin[f] = (int32_t)n_in;"
+old = "out_nin[f] = (int32_t)u.n_in;"
 assert src.count(old) == 1, "ransac.hip: the n_inliers store moved"
-open(path, "w").write(src.replace(old, "out_nin[f] = exact ? -1000 - (int32_t)n_in : (int32_t)n_in;"))
+open(path, "w").write(src.replace(old, "out_nin[f] = exact ? -1000 - (int32_t)u.n_in : (int32_t)u.n_in;"))

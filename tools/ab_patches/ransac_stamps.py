@@ -35,8 +35,8 @@ sub("using namespace ransac_common;\n",
 sub("  const int tid = threadIdx.x;\n  const int lane = tid & 63, wave = tid >> 6;\n  int p0, N, hoff;\n",
     "  const int tid = threadIdx.x;\n  const int lane = tid & 63, wave = tid >> 6;\n  STAMP(0);\n"
     "  __shared__ int s_na2, s_nb;\n  if (tid == 0) { s_na2 = 0; s_nb = 0; }\n  int p0, N, hoff;\n")
-sub("    __syncthreads();\n  }\n\n  const Pts P{sx, sy, dxs, dys};\n",
-    "    __syncthreads();\n  }\n  STAMP(1);\n\n  const Pts P{sx, sy, dxs, dys};\n")
+sub("  stage_points<LARGE>(gather, N, sx, sy, dxs, dys, pk32, red, mg);\n",
+    "  stage_points<LARGE>(gather, N, sx, sy, dxs, dys, pk32, red, mg);\n  STAMP(1);\n")
 sub("    __syncthreads();  // sc.cnt is reused\n", "    __syncthreads();  // sc.cnt is reused\n    STAMP(2);\n")
 sub("          const Model m = fit_of(tc);\n          int c = 0;\n",
     "          const Model m = fit_of(tc);\n          if (lane == 0) atomicAdd(&s_na2, 1);\n          int c = 0;\n")
@@ -49,8 +49,8 @@ sub("          const Model m = fit_of(tc);\n          const double S = wave_pair
     "          const double S = wave_pairwise<LARGE>(\n")
 sub("  select_best(best, any_zero, T, tS, tC, sc, s_any_zero, best_t, best_c);\n",
     "  select_best(best, any_zero, T, tS, tC, sc, s_any_zero, best_t, best_c);\n  STAMP(6);\n")
-sub("    out_nin[f] = (int32_t)n_in;\n    out_best[f] = best_t;\n  }\n",
-    "    out_nin[f] = (int32_t)n_in;\n    out_best[f] = best_t;\n  }\n  STAMP(7);\n  STAMP_V(8, s_na2);\n"
+sub("    out_nin[f] = (int32_t)u.n_in;\n    out_best[f] = best_t;\n  }\n",
+    "    out_nin[f] = (int32_t)u.n_in;\n    out_best[f] = best_t;\n  }\n  STAMP(7);\n  STAMP_V(8, s_na2);\n"
     "  STAMP_V(9, s_nb);\n")
 s += ("\nextern \"C\" int kcmc_debug_ransac_stamps(void* dst, int n_frames) {\n"
       "  const size_t n = (size_t)(n_frames < kcmc::kStampFrames ? n_frames : kcmc::kStampFrames) * kcmc::kStamps;\n"
