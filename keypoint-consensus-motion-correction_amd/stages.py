@@ -704,13 +704,22 @@ def warp_field_u16(frames: torch.Tensor, affines: torch.Tensor, field_q: torch.T
 
 
 # ------------------------------------------------------------ f2: normalisation
+def _percentile_fraction(q: float) -> np.float64:
+    """q / 100 as np.percentile forms it, or its ValueError: numpy tests the quotient, not q."""
+    qq = np.true_divide(np.float64(q), 100)
+    if not 0.0 <= qq <= 1.0:
+        raise ValueError("Percentiles must be in the range [0, 100]")
+    return qq
+
+
 def _numpy_linear_percentile(n: int, q: float, value_at) -> np.float64:
     """np.percentile(a, q) (default 'linear' method) of a flattened integer array of n
     elements, given value_at(rank) = the rank-th smallest element: numpy's virtual
     index (n - 1) * q' with q' = q/100 (numpy >= 1.22 'linear'), floor/next ranks
     clipped to the array, and its _lerp (a + (b-a)*t, or b - (b-a)*(1-t) when t >= 0.5),
-    evaluated with the same float64 operations."""
-    qq = np.true_divide(np.float64(q), 100)
+    evaluated with the same float64 operations.  ValueError where numpy raises it: q / 100
+    outside [0, 1], NaN included."""
+    qq = _percentile_fraction(q)
     vi = (n - 1) * qq
     prev = np.floor(vi)
     if vi >= n - 1:
@@ -738,7 +747,9 @@ def brightest_px(frames, percentile: float = 99.99) -> np.float64:
     """VA:479-482 on the device: np.percentile(images, 99.99) of a uint16 stack, exact
     (two order statistics from two histogram passes, numpy's interpolation on the host).
     ``frames``: one device tensor, or the slabs of one stack on several devices (their
-    histograms are summed: the percentile of the whole stack)."""
+    histograms are summed: the percentile of the whole stack).  ValueError for a percentile
+    outside [0, 100] or NaN, as numpy raises it."""
+    _percentile_fraction(percentile)  # before any launch
     parts = [frames] if isinstance(frames, torch.Tensor) else list(frames)
     for p in parts:
         _require(p, "frames", torch.uint16, _device_of(p))

@@ -11,6 +11,8 @@ runs one case on the device and compares it with the numpy restatement, bit for 
     resize_u8           kcmc_resize_u8                              (kcmc_amd.stages)
     warp_affine         kcmc_warp_affine_u16, C = 1 / 3 / 4         (kcmc_amd.stages; against the C oracle)
     warp_perspective    kcmc_warp_perspective_u16, C = 1 / 3 / 4    (kcmc_amd.stages; against the C oracle)
+    normalize           kcmc_histogram_u16 + kcmc_lut_u16_to_u8     (kcmc_amd.stages.brightest_px /
+                        max_scale_u8; against np.percentile and the reference's scaling expression)
 
 case_<kernel>(seed) draws one case from np.random.default_rng(seed): the inputs as numpy arrays
 and the drawn parameters (describe(case): what a failure message prints).  expected(kernel, case)
@@ -47,7 +49,7 @@ import test_refine_host as rhost
 
 # _rng seeds from a kernel's position here: new kernels go at the end
 KERNELS = ("frame_stats", "shift_search", "gradient_sums", "tile_gradient_sums", "phase_sums", "warp_field",
-           "resize_u8", "warp_affine", "warp_perspective")
+           "resize_u8", "warp_affine", "warp_perspective", "normalize")
 # the seeds of tests/test_gpu_sweeps.py; tests/test_sweep_cases_host.py holds what they must reach
 SEEDS = {k: tuple(range(16)) for k in KERNELS}
 # seeds 0 to 15 hold no multichannel frame staged by mode 0 from a source 8 bytes off the 16-byte grid
@@ -390,6 +392,38 @@ def case_warp_perspective(seed):
     return _case_linear("warp_perspective", seed)
 
 
+NORMALIZE_Q = (99.99, 0.0, 100.0, 50.0)
+
+
+def case_normalize(seed):
+    """F in 1..6, H in 1..300, W in 1..300 (_width's rule): up to 540 000 values, below every grid
+    cap (the capped grids are tests/test_gpu_normalize.py's).  Values: the shared families, one
+    case in four the concentrated one ([0x0F00, 0x10FF]: two coarse bins, the fine pass counts
+    about half the stack).  The slabs go to brightest_px as a part list, each at its OFFS_U16
+    offset (1 and 4 elements: copied for alignment); max_scale_u8 writes each slab into an ``out``
+    view 0, 1, 4 or 8 bytes into a sentinel-filled buffer.  q is drawn from NORMALIZE_Q and one
+    uniform value; seed % 8 == 3 and 7 instead take the q whose two ranks lie on the two sides of
+    the stack's first coarse-bin boundary, with gamma about 0.25 and 0.75 (kept as drawn when all
+    values share a coarse bin)."""
+    rng = _rng("normalize", seed)
+    F, H, W = int(rng.integers(1, 7)), int(rng.integers(1, 301)), _width(rng, 1, 300)
+    if rng.integers(0, 4) == 0:
+        frames, family = rng.integers(0x0F00, 0x1100, (F, H, W)).astype(np.uint16), "concentrated"
+    else:
+        frames, family = _values(rng, (F, H, W)), "shared"
+    case = {"F": F, "H": H, "W": W, "family": family, "frames": frames, "slabs": _layout(rng, F, OFFS_U16)}
+    case["out_offs"] = [int(rng.choice(OFFS_U16)) for _ in case["slabs"]]
+    uniform = float(rng.uniform(0, 100))
+    case["percentile"] = (NORMALIZE_Q + (uniform,))[int(rng.integers(0, 5))]
+    case["max_px"] = int(rng.choice((255, 127)))
+    if seed % 8 in (3, 7):
+        hb = np.sort(frames.reshape(-1) >> 8)
+        edge = np.flatnonzero(hb[1:] != hb[:-1])
+        if len(edge):
+            case["percentile"] = 100.0 * (int(edge[0]) + (0.25 if seed % 8 == 3 else 0.75)) / (frames.size - 1)
+    return case
+
+
 def frame_slab(case, f):
     """(source offset, output offset) of the slab that holds frame f."""
     return next((off, o) for (a, b, off), o in zip(case["slabs"], case.get("out_offs", [0] * 3)) if a <= f < b)
@@ -398,7 +432,7 @@ def frame_slab(case, f):
 GENERATORS = {"frame_stats": case_frame_stats, "shift_search": case_shift_search, "gradient_sums": case_gradient_sums,
               "tile_gradient_sums": case_tile_gradient_sums, "phase_sums": case_phase_sums,
               "warp_field": case_warp_field, "resize_u8": case_resize_u8, "warp_affine": case_warp_affine,
-              "warp_perspective": case_warp_perspective}
+              "warp_perspective": case_warp_perspective, "normalize": case_normalize}
 
 
 def describe(case):
@@ -447,7 +481,17 @@ def expected(kernel, case):
         ref = oracle.warp_affine_u16 if kernel == "warp_affine" else oracle.warp_perspective_u16
         return {"out": np.stack([np.zeros_like(fr[f]) if np.isnan(case["M"][f]).any() else
                                  ref(fr[f], case["M"][f], inverse_map=case["inverse_map"]) for f in range(F)])}
+    if kernel == "normalize":
+        # numpy's own percentile and the reference's expression (VA:481, VA:490), never stages.max_scale_lut
+        b, max_px = np.percentile(fr, case["percentile"]), case["max_px"]
+        return {"brightest": b, "out": np.clip(fr / scale_divisor(b) * max_px, a_min=0, a_max=max_px).astype(np.uint8)}
     raise KeyError(kernel)
+
+
+def scale_divisor(b):
+    """What the normalize sweep scales by: the percentile's value, or 1.0 where that is 0 (q = 0 on
+    a stack that holds a zero), which the reference's expression would divide by."""
+    return b if b > 0 else np.float64(1.0)
 
 
 # ------------------------------------------------------------------ the device's answers
@@ -521,6 +565,11 @@ def run(kernel, case, dev):
             out, ok = _per_slab(case, dev, torch.uint8, GUARD_U8, (case["dst_h"], case["dst_w"]), call)
         return {"out": out, "guards": ok}
     parts = _parts(case, dev)
+    if kernel == "normalize":
+        b = stages.brightest_px(parts, case["percentile"])
+        call = lambda src, a, b_, o: stages.max_scale_u8(src, scale_divisor(b), out=o, max_px=case["max_px"])  # noqa: E731
+        out, ok = _per_slab(case, dev, torch.uint8, GUARD_U8, (case["H"], case["W"]), call)
+        return {"brightest": b, "out": out, "guards": ok}
     if kernel == "phase_sums":
         return {"sums": bidi.phase_sums(parts, case["idx"], case["R"])}
     ref = _view(case["ref"], case["ref_off"], dev)

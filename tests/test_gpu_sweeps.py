@@ -2,7 +2,8 @@
 the field warp, the bidirectional-scan phase sums, the exact resize) against their numpy
 restatements, and of the two bilinear warps (one, three and four channels, sources and outputs
 on and off the 16- and 4-byte grids their vector loads and stores assume) against the C oracle,
-bit for bit: tests/sweep_cases.py draws the cases (shapes, rectangles, tilings,
+and of the normalisation front end (part lists, percentiles) against np.percentile and the
+reference's scaling expression, bit for bit: tests/sweep_cases.py draws the cases (shapes, rectangles, tilings,
 radii, fields, maps, slab layouts with misaligned starts, index lists with holes) and compares;
 tests/test_sweep_cases_host.py holds what the committed seeds reach.  Outputs with an ``out``
 argument are written into the middle of a sentinel-filled buffer whose sentinels must survive.
@@ -62,3 +63,10 @@ def test_warp_affine_sweep(dev, seed):
 @pytest.mark.parametrize("seed", _seeds("warp_perspective"))
 def test_warp_perspective_sweep(dev, seed):
     sc.check("warp_perspective", seed, dev)
+
+
+@pytest.mark.parametrize("seed", _seeds("normalize"))
+def test_normalize_sweep(dev, seed):
+    """stages.brightest_px over the slabs as a part list == np.percentile, and max_scale_u8 of
+    every slab == the reference's expression at that value."""
+    sc.check("normalize", seed, dev)

@@ -240,6 +240,21 @@ def test_percentile_restatement_matches_numpy():
         q = float(rng.choice([99.99, 50.0, 0.0, 100.0, 12.5, rng.uniform(0, 100)]))
         s = np.sort(a)
         assert _numpy_linear_percentile(n, q, lambda r: int(s[r])) == np.percentile(a, q)
+    # q outside [0, 100] and NaN: numpy's ValueError, exactly where numpy raises it (it tests q / 100,
+    # so the neighbours of 0 and 100 are asked of numpy, not assumed)
+    a = np.arange(10, dtype=np.uint16)
+    for q in (-1.0, -1e-300, 100.001, 1e9, np.inf, -np.inf, np.nan, np.nextafter(100.0, 200.0),
+              np.nextafter(0.0, -1.0), -0.0, np.nextafter(100.0, 0.0)):
+        try:
+            want = np.percentile(a, q)
+        except ValueError:
+            with pytest.raises(ValueError, match="range"):
+                _numpy_linear_percentile(10, q, lambda r: int(a[r]))
+        else:
+            assert _numpy_linear_percentile(10, q, lambda r: int(a[r])) == want, q
+    for q in (-1.0, 100.001, np.nan):
+        with pytest.raises(ValueError):
+            np.percentile(a, q)
 
 
 def test_max_scale_lut_matches_reference_expression():

@@ -8,6 +8,7 @@ import pytest
 import oracle
 import sweep_cases as sc
 import test_fallback_host as fhost
+import test_normalize_host as nhost
 import test_piecewise_host as phost
 import test_quality_host as qhost
 import test_refine_field_host as tfhost
@@ -132,6 +133,51 @@ def test_resize_seeds(cases):
     assert any(1 in (c["H"], c["W"], c["dst_h"], c["dst_w"]) for c in cs)
     assert any(c["dst_h"] == c["H"] or c["dst_w"] == c["W"] for c in cs)
     assert all(1 <= v <= 400 for c in cs for v in (c["H"], c["W"], c["dst_h"], c["dst_w"]))
+
+
+def test_normalize_seeds(cases):
+    """What only this sweep puts in front of stages.brightest_px: part lists with copied parts
+    and every tail length, and percentiles whose two ranks (test_normalize_host.ranks) sit in
+    different coarse bins, on both branches of numpy's interpolation."""
+    cs = cases["normalize"]
+    split, gammas = 0, []
+    for c in cs:
+        s = np.sort(c["frames"].reshape(-1))
+        lo, hi, gamma = nhost.ranks(s.size, c["percentile"])
+        if s[lo] >> 8 != s[hi] >> 8:  # a fine pass per rank
+            split += 1
+            gammas.append(gamma)
+    assert split >= 1
+    assert any(g >= 0.5 for g in gammas) and any(0 < g < 0.5 for g in gammas)  # among the split ones
+    all_g = [nhost.ranks(c["frames"].size, c["percentile"])[2] for c in cs]
+    assert any(g >= 0.5 for g in all_g) and any(g < 0.5 for g in all_g)
+    parts = [((b - a) * c["H"] * c["W"], off) for c in cs for a, b, off in c["slabs"]]
+    assert any(off % 8 for _, off in parts)  # not on the 16-byte grid: stages._aligned16 copies it
+    assert {n % 8 for n, _ in parts} == set(range(8))
+    assert any(isinstance(sc._parts(c, "cpu"), list) for c in cs)  # handed over as a part list
+    # the draws of the generator's docstring
+    assert {c["family"] for c in cs} == {"shared", "concentrated"}
+    assert {c["max_px"] for c in cs} == {255, 127}
+    assert set(sc.NORMALIZE_Q) <= {c["percentile"] for c in cs}
+    assert any(c["percentile"] not in sc.NORMALIZE_Q for c in cs)
+    assert all(1 <= c["F"] <= 6 and 1 <= c["H"] <= 300 and 1 <= c["W"] <= 300 for c in cs)
+    assert all(0.0 <= c["percentile"] <= 100.0 for c in cs)
+
+
+def test_normalize_expected_is_numpys_and_compare_is_sensitive():
+    c = next(c for c in map(sc.case_normalize, sc.SEEDS["normalize"]) if c["frames"].size > 1000)
+    want = sc.expected("normalize", c)
+    assert want["brightest"] == np.percentile(c["frames"], c["percentile"])
+    assert want["out"].dtype == np.uint8 and want["out"].shape == c["frames"].shape
+    sc.compare("normalize", c, {"brightest": want["brightest"], "out": want["out"].copy(), "guards": True}, want)
+    wrong = want["out"].copy()
+    wrong.reshape(-1)[-1] ^= 1
+    for got in ({"brightest": want["brightest"], "out": wrong, "guards": True},
+                {"brightest": np.nextafter(want["brightest"], np.inf), "out": want["out"], "guards": True},
+                {"brightest": want["brightest"], "out": want["out"], "guards": False}):
+        with pytest.raises(AssertionError):
+            sc.compare("normalize", c, got, want)
+    assert sc.scale_divisor(np.float64(0.0)) == 1.0 and sc.scale_divisor(np.float64(3.5)) == 3.5
 
 
 # ------------------------------------------------------------------ the bilinear warps
