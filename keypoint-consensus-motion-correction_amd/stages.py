@@ -382,7 +382,7 @@ def consensus_lookup(keep_bits: torch.Tensor, n_tpl: int, pack_dev: torch.Tensor
     L = _lib.load()
     pt_off = torch.empty(F + 1, dtype=torch.int32, device=dev)
     pt_idx = torch.empty(max(F * nc, 1), dtype=torch.int32, device=dev)
-    # the set tables that do not fit in LDS (0 bytes for nc < 308: table size <= 1024)
+    # the set tables that do not fit in LDS (0 bytes for nc <= 306: table size <= 512)
     sb = int(L.kcmc_consensus_lookup_scratch_bytes(F, nc))
     scratch = torch.empty(sb, dtype=torch.uint8, device=dev) if sb > 0 else None
     _lib.check(L.kcmc_consensus_lookup(_ctx(dev).handle, _ptr(keep_bits), F, int(n_tpl), _ptr(pack_dev), int(nc),
